@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- queries/s of the query() hot path on MI355X, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2], "cfg3"): N=10M points, d=128, k=10, tries=10, float, Q=10k queries per GPU per
@@ -19,8 +19,13 @@ so per-GPU gather work stays fixed: "scaling": "weak".  value = total queries / 
 "strong" reports the same job with the batch FIXED at 10k queries in total.  The index is built by all ranks together
 (precomp_sharded: every rank holds all rows during the build, the distance passes are dealt out by bucket).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step` = one timed step, no
+HIP event inside the timed region).  --dump-outputs DIR also writes the last timed step's results as DIR/ids.npy
+(float64) and DIR/dists.npy (the run's float type); the inputs depend only on the arguments, so two builds can be compared
+output for output.  With --full the timed region carries the HIP-event pair around each stage-1 launch, and the JSON
+line also carries
   roofline     : the dominant kernel (stage1_select) priced at its ALGORITHMIC bytes / HIP-event duration
+  stage_ms / recall_sample / overlap (N=1), strong / replicas (N > 1): see below
   cpu_baseline : the reference's own query_cpu (oracle/_ref) or the oracle (CPU restatement), 1 core, timed on a bounded
                  sample of the same workload on the same index, on rank 0 at N=1 only -- and compared with the GPU's
                  results (parity).
@@ -72,6 +77,12 @@ def parse():
     ap.add_argument("--tune-seconds", type=float, default=20.0,
                     help="N > 1: wall-clock budget of the in-place schedule measurement before the warm-up (0 = keep the "
                          "pinned schedule)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's ids and squared distances to DIR/ids.npy and DIR/dists.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline and per-stage times, recall sample, "
+                         "overlap, host-pointer API and CPU baseline (N=1; --no-* switch them off one by one), strong "
+                         "scaling and replicas (N > 1)")
     return ap.parse_args()
 
 
@@ -260,7 +271,7 @@ def main():
         with park_random():
             shard = points[lo:hi].clone()
             ix.reshard(shard, lo, hi)
-            if args.no_replicas_extra:
+            if not args.full or args.no_replicas_extra:
                 del points
             torch.cuda.empty_cache()
         runner = ShardedQuery(ix, dist, lanes=7)   # exchange agreed on by all ranks at start-up (all-to-all, else all-gather)
@@ -277,7 +288,8 @@ def main():
             runner.autotune(batches[0], budget_s=args.tune_seconds)
 
         def run_steps(ys):
-            runner.pump(ys)
+            res = runner.pump(ys)
+            return res[-1] if res else None
     else:
         ns = max(1, args.streams)
         out_ids = [torch.empty((Q, k), dtype=torch.int64, device=device) for _ in range(ns)]
@@ -285,12 +297,17 @@ def main():
         lanes = [(ix.workspace(), torch.cuda.Stream(device=device)) for _ in range(ns)] if ns > 1 else None
 
         def run_steps(ys):
+            """-> (ids, dists) of the last batch (device tensors, complete after a synchronize)"""
+            last = None
             for i, y in enumerate(ys):
                 if ns == 1:
                     ix.query(y, out_ids=out_ids[0], out_dists=out_d[0])
+                    last = out_ids[0], out_d[0]
                 else:
                     j = i % ns
                     ix.query(y, out_ids=out_ids[j], out_dists=out_d[j], ws=lanes[j][0], stream=lanes[j][1])
+                    last = out_ids[j], out_d[j]
+            return last
 
     def barrier():
         if sharded:
@@ -301,7 +318,7 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        (run or run_steps)(ys)
+        res = (run or run_steps)(ys)
         submit = time.perf_counter() - t0
         torch.cuda.synchronize()
         barrier()
@@ -310,54 +327,38 @@ def main():
             tt = torch.tensor([el], dtype=torch.float64, device=coll_dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        return el, submit
+        return el, submit, res
 
     run_steps(batches[:args.warmup])
     torch.cuda.synchronize()
     ix.stats(reset=True)
-    # Inside the timed region: ONLY the HIP-event pair around each stage-1 launch (the roofline's kernel time, measured on
-    # the steps that count).  Every event record costs ~5 us of stream time, so the per-stage marks (8 more events per
-    # step) and the gathered-row statistics (one more small kernel per step) come from a SEPARATE, untimed pass over the
-    # same K batches right afterwards -- same batches, same rows, same flagged queries.
-    ix.profile(2 if os.environ.get("ANN_BENCH_NO_EVENTS") != "1" else 0)
-    elapsed, submit_s = timed(batches[args.warmup:])
-    st = ix.stats()
-    ix.profile(True)
-    ix.stats(reset=True)
-    run_steps(batches[args.warmup:])
-    torch.cuda.synchronize()
-    st_full = ix.stats()
-    stage_ms = ix.stage_ms() if not sharded else None
-    ix.profile(False)
-    if not st["s1_launches"]:  # ANN_BENCH_NO_EVENTS=1: no kernel time from the timed region; report the separate pass's
-        st["s1_launches"], st["s1_ms"] = st_full["s1_launches"], st_full["s1_ms"]
-    for key in ("s1_rows", "other_rows", "queries", "exact_queries", "tie_queries"):
-        st[key] = st_full[key]
-
-    # ---- roofline of the dominant kernel (stage1_select): algorithmic bytes / HIP-event time
-    launches = max(st["s1_launches"], 1.0)
-    v1 = st["s1_rows"] / max(st["queries"], 1.0)            # rows THIS device gathered per query
-    kern_ms = st["s1_ms"] / launches
-    bytes_per_query = v1 * d * esz + ix.P1 * 4 + d * esz + T * 4 + (k + 1) * (esz + 4)
-    bytes_per_launch = bytes_per_query * Q
-    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": "stage1_select_kernel<%d>" % d, "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                "rows_gathered_per_query": round(v1, 1)}
-    if sharded:
-        roofline["note"] = "rank 0's kernel; with several batches in flight it overlaps the other batches's small kernels"
-
-    # PMC counters cannot be read in-process: for the default workload the figure is the committed rocprofv3 --pmc
-    # measurement of this same command (profiles/traffic.json says which run); any other workload reports null.
+    # Inside the timed region (--full only): ONLY the HIP-event pair around each stage-1 launch (the roofline's kernel time,
+    # measured on the steps that count).  Every event record costs ~5 us of stream time, so the per-stage marks (8 more
+    # events per step) and the gathered-row statistics (one more small kernel per step) come from a SEPARATE, untimed pass
+    # over the same K batches right afterwards -- same batches, same rows, same flagged queries.  A plain run records no
+    # event at all.
+    ix.profile(2 if args.full and os.environ.get("ANN_BENCH_NO_EVENTS") != "1" else 0)
+    elapsed, submit_s, last = timed(batches[args.warmup:])
+    st = ix.stats()             # the flagged-query counts: kept with profiling on or off
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, np)
+    last = None
+    if args.full:
+        ix.profile(True)
+        ix.stats(reset=True)
+        run_steps(batches[args.warmup:])
+        torch.cuda.synchronize()
+        st_full = ix.stats()
+        stage_ms = ix.stage_ms() if not sharded else None
+        ix.profile(False)
+        if not st["s1_launches"]:  # ANN_BENCH_NO_EVENTS=1: no kernel time from the timed region; report the separate pass's
+            st["s1_launches"], st["s1_ms"] = st_full["s1_launches"], st_full["s1_ms"]
+        for key in ("s1_rows", "other_rows", "queries", "exact_queries", "tie_queries"):
+            st[key] = st_full[key]
+        roofline = roofline_of(st, ix, n, d, k, T, Q, esz, sharded)
+    else:
+        stage_ms = None
     tag, wl_short, wl_long = describe(n, d, k, T, Q, args.dtype)
-    try:
-        tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-        if not sharded and (n, d, k, T, Q, args.dtype) == (10_000_000, 128, 10, 10, 10_000, "f32"):
-            roofline["traffic"] = tr["traffic_bytes_per_launch"]
-            roofline["traffic_source"] = "static, from the committed rocprofv3 --pmc passes: " + tr["source"]
-    except (OSError, ValueError, KeyError):
-        pass
 
     value = Q * args.steps / elapsed
     line = {"metric": "queries/sec, %s (query(): hash + candidate gather + L2 + top-k + refine)" % wl_short,
@@ -375,8 +376,9 @@ def main():
                        "precomp_s": round(precomp_s, 2),
                        "exact_path_queries_per_step": round(st["exact_queries"] / args.steps, 2),
                        "tie_path_queries_per_step": round(st.get("tie_queries", 0) / args.steps, 2),
-                       "host_submit_ms_per_step": round(submit_s / args.steps * 1e3, 4)},
-            "roofline": roofline}
+                       "host_submit_ms_per_step": round(submit_s / args.steps * 1e3, 4)}}
+    if args.full:
+        line["roofline"] = roofline
     if stage_ms:
         line["config"]["stage_ms_per_step"] = {k_: round(v / args.steps, 4) for k_, v in stage_ms.items()}
         line["config"]["stage_ms_source"] = ("a separate untimed pass over the same batches with 8 more HIP events per step (~5 us "
@@ -394,13 +396,13 @@ def main():
                                   "in flight), its `value` is strictly serial" % runner.depth)
 
     # ---- N > 1 extra: strong scaling -- the batch FIXED at --queries in total (10k), sharded the same way
-    if sharded and not args.no_strong_extra:
+    if sharded and args.full and not args.no_strong_extra:
         Qs = args.q
         ys = [b[:Qs].contiguous() for b in batches]
         if not pin and args.tune_seconds > 0:
             runner.autotune(ys[0], budget_s=args.tune_seconds / 2)   # a batch this small wants its own schedule
         run_steps(ys[:args.warmup])
-        el_s, _ = timed(ys[args.warmup:])
+        el_s, _, _ = timed(ys[args.warmup:])
         line["strong"] = {"queries_per_step_total": Qs, "value": round(Qs * args.steps / el_s, 1), "unit": "queries/s",
                           "ms_per_step": round(el_s / args.steps * 1e3, 4),
                           "schedule": {k_: v for k_, v in (runner.tuned or {}).items() if k_ != "table"},
@@ -410,13 +412,13 @@ def main():
     # ---- N > 1 extra: the other way to split the job: every GPU keeps ALL rows (cfg4's 20 GB fit each
     #      288-GB GPU) and answers 1/N of the queries of every batch; one all-gather of the hash codes is the only exchange
     #      before the results.  Not the mandated row-sharded line -- the bound that line should be judged against.
-    if sharded and not args.no_replicas_extra:
+    if sharded and args.full and not args.no_replicas_extra:
         from approximatenn_amd.sharded import ReplicaQuery
         with park_random():
             ix.reshard(points, 0, n)            # all rows again
             rq = ReplicaQuery(ix, dist, lanes=2, gather=True)
         rq.pump(batches[:max(args.warmup, 2)])
-        el_r, _ = timed(batches[args.warmup:], rq.pump)
+        el_r, _, _ = timed(batches[args.warmup:], rq.pump)
         line["replicas"] = {"queries_per_step_total": Q, "value": round(Q * args.steps / el_r, 1), "unit": "queries/s",
                             "ms_per_step": round(el_r / args.steps * 1e3, 4), "batches_in_flight": rq.depth,
                             "note": "query-sharded: every GPU holds all %d rows and answers Q/N queries of each batch; "
@@ -425,7 +427,7 @@ def main():
 
     # ---- extra: the same K steps with consecutive batches overlapped on two streams (annhip_query_on); reported
     #      beside `value`, never instead of it: per-launch kernel times are not meaningful while gathers overlap
-    if not sharded and rank == 0 and max(1, args.streams) == 1 and not args.no_overlap_extra:
+    if args.full and not sharded and rank == 0 and max(1, args.streams) == 1 and not args.no_overlap_extra:
         lanes2 = [(ix.workspace(), torch.cuda.Stream(device=device)) for _ in range(2)]
         o_ids = [torch.empty((Q, k), dtype=torch.int64, device=device) for _ in range(2)]
         o_d = [torch.empty((Q, k), dtype=tdt, device=device) for _ in range(2)]
@@ -440,7 +442,7 @@ def main():
                            "ms_per_step": round(dt / args.steps * 1e3, 4),
                            "note": "consecutive batches on 2 HIP streams/workspaces; same work, same results"}
     # ---- quality of the answers (not part of the metric): exact-rank recall of a 512-query sample, by GPU brute force
-    if not sharded and rank == 0:
+    if args.full and not sharded and rank == 0:
         qs = min(512, Q)
         g_ids, _, _ = ix.query(batches[0][:qs].contiguous())
         rk = A.recall_ranks(points, batches[0][:qs].contiguous(), g_ids)
@@ -463,7 +465,7 @@ def main():
         line["config"]["recall_sample"]["fixed_mode"] = dict({kk: round(v, 4) for kk, v in A.recall_summary(rk, k).items()},
                                                              ms_per_step=f_ms)
     # ---- host-pointer API + CPU baseline share one exported save_t and one host copy of the points
-    if not sharded and rank == 0 and not (args.no_cpu_baseline and args.no_host_api):
+    if args.full and not sharded and rank == 0 and not (args.no_cpu_baseline and args.no_host_api):
         if host_pts is None:
             host_pts = points.cpu().numpy()
         save = ix.export()
@@ -477,6 +479,54 @@ def main():
     ix.close()
     if sharded:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, last, np):
+    """--dump-outputs: the last timed step's results as a caller of query() receives them -- ids.npy (float64; ids are
+    below 2^53, so exact) and dists.npy (float32 or float64 as computed).  Past 64 MB in all, a fixed seeded sample of
+    rows is written instead, and rows.npy (float64) says which."""
+    ids = last[0].cpu().numpy().astype(np.float64)
+    dists = last[1].cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    row_bytes = ids.shape[1] * (ids.itemsize + dists.itemsize)
+    if ids.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - (1 << 20)) // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], size=keep, replace=False))
+        ids, dists = ids[rows], dists[rows]
+        np.save(os.path.join(outdir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(outdir, "ids.npy"), ids)
+    np.save(os.path.join(outdir, "dists.npy"), dists)
+
+
+def roofline_of(st, ix, n, d, k, T, Q, esz, sharded):
+    """--full: the dominant kernel (stage1_select) priced at its algorithmic bytes / HIP-event time."""
+    dtype = "f32" if esz == 4 else "f64"
+    launches = max(st["s1_launches"], 1.0)
+    v1 = st["s1_rows"] / max(st["queries"], 1.0)            # rows THIS device gathered per query
+    kern_ms = st["s1_ms"] / launches
+    bytes_per_query = v1 * d * esz + ix.P1 * 4 + d * esz + T * 4 + (k + 1) * (esz + 4)
+    bytes_per_launch = bytes_per_query * Q
+    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    roofline = {"bound": "hbm", "kernel": "stage1_select_kernel<%d>" % d, "achieved": round(achieved, 1),
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": int(bytes_per_launch),
+                "rows_gathered_per_query": round(v1, 1)}
+    if sharded:
+        roofline["note"] = "rank 0's kernel; with several batches in flight it overlaps the other batches's small kernels"
+
+    # PMC counters cannot be read in-process: for the default workload the figure is the committed rocprofv3 --pmc
+    # measurement of this same command (profiles/traffic.json says which run); any other workload reports null.
+    try:
+        tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+        if not sharded and (n, d, k, T, Q, dtype) == (10_000_000, 128, 10, 10, 10_000, "f32"):
+            roofline["traffic"] = tr["traffic_bytes_per_launch"]
+            roofline["traffic_source"] = "static, from the committed rocprofv3 --pmc passes: " + tr["source"]
+    except (OSError, ValueError, KeyError):
+        pass
+    return roofline
 
 
 def host_api(args, ix, save, host_pts, batches, np, torch, A):

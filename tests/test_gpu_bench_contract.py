@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", "200000", "--queries", "2000", "--steps", "4",
-                          "--warmup", "1", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -39,10 +40,40 @@ def test_bench_line_contract():
     assert h["stream_3_lanes"]["value"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline fields only (the extras need --full), and --dump-outputs writes the last timed step's
+    results; the same arguments give the same inputs, hence bit-identical outputs in a second run."""
+    def run(outdir):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", "200000", "--queries", "2000",
+                              "--steps", "3", "--warmup", "1", "--dump-outputs", str(outdir)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "queries/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and "N=200k d=128 k=10 Q=2k float" in d["metric"]
+    assert abs(d["value"] - 2000 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-3
+    for key in ("roofline", "cpu_baseline", "host_api", "overlap"):
+        assert key not in d, key
+    assert "stage_ms_per_step" not in d["config"] and "recall_sample" not in d["config"]
+    ids, dists = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "dists.npy")
+    assert ids.dtype == np.float64 and dists.dtype == np.float32 and ids.shape == dists.shape == (2000, 10)
+    assert np.all(ids == np.floor(ids)) and ids.min() >= 0 and ids.max() < 200000
+    assert np.all(np.isfinite(dists)) and dists.min() >= 0
+    run(tmp_path / "b")
+    assert np.array_equal(np.load(tmp_path / "b" / "ids.npy"), ids)
+    assert np.array_equal(np.load(tmp_path / "b" / "dists.npy").view(np.uint32), dists.view(np.uint32))
+
+
 def test_bench_labels_follow_dtype_and_shape():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", "60000", "--dim", "64", "--knn", "12",
                           "--queries", "500", "--steps", "2", "--warmup", "1", "--dtype", "f64", "--data", "randn",
-                          "--no-cpu-baseline", "--no-host-api"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-cpu-baseline", "--no-host-api", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["dtype"] == "f64" and "N=60k d=64 k=12 Q=500 double" in d["metric"] and "double" in d["config"]["workload"]
@@ -55,7 +86,7 @@ def test_bench_multi_rank_branch_two_ranks_sharing_the_gpu():
     env = dict(os.environ, ANN_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29633", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points", "200000", "--queries", "1000",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -71,13 +102,13 @@ def test_bench_multi_rank_branch_two_ranks_sharing_the_gpu():
     assert r["queries_per_step_total"] == 2000 and r["value"] > 0
 
 
-def test_bench_launches_its_own_ranks():
+def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with NO torchrun around it -- how the driver starts every bench line: the script
     starts its ranks as a fresh child process before anything touches the GPU, relays the one JSON line and the exit status."""
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ANN_BENCH_SHARED_GPU"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points", "200000", "--queries", "1000",
-           "--steps", "2", "--warmup", "1", "--no-strong-extra", "--tune-seconds", "5"]
+           "--steps", "2", "--warmup", "1", "--no-strong-extra", "--tune-seconds", "5", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -88,6 +119,8 @@ def test_bench_launches_its_own_ranks():
     assert r["world_size"] == 2 and r["backend"] == "gloo" and len(r["index_checksum"]) == 16
     sch = d["config"]["schedule"]
     assert sch["table"][0]["depth"] == 3 and sch["table"][0]["split"] is True      # the pinned schedule is measured first
+    ids, dists = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "dists.npy")   # rank 0 writes the whole batch's results
+    assert ids.shape == dists.shape == (2000, 10) and ids.min() >= 0 and ids.max() < 200000
     # failing ranks give a non-zero exit status and no JSON line (here: an empty point set, which the library refuses)
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points", "0"], capture_output=True,
                          text=True, timeout=600, cwd=ROOT, env=env)
@@ -100,7 +133,7 @@ def test_bench_multi_rank_fallback_exchange():
     env = dict(os.environ, ANN_BENCH_SHARED_GPU="1", ANN_SHARD_EXCHANGE="allgather")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29634", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points", "100000", "--queries", "500",
-           "--steps", "2", "--warmup", "1", "--data", "randn", "--no-strong-extra"]
+           "--steps", "2", "--warmup", "1", "--data", "randn", "--no-strong-extra", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
@@ -114,7 +147,7 @@ def test_bench_single_rank_over_rccl():
     env = dict(os.environ, ANN_SHARD_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29635", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--points", "200000", "--queries", "2000",
-           "--steps", "3", "--warmup", "1", "--data", "randn"]
+           "--steps", "3", "--warmup", "1", "--data", "randn", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])

@@ -3,8 +3,9 @@
 # environment setting, interleaved twice (box drift shows as the difference between the two rounds).  One line each.
 for round in 1 2; do
 for setting in "$@"; do
-  env $setting python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-host-api --data randn > gpurun_out/ab_env.log 2>&1
-  python3 - "$setting" gpurun_out/ab_env.log <<'PY'
+  log=$(mktemp)
+  env $setting python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-host-api --data randn > "$log" 2>&1
+  python3 - "$setting" "$log" <<'PY'
 import json, sys
 name, path = sys.argv[1:3]
 line = [l for l in open(path) if l.startswith("{")]
@@ -16,5 +17,6 @@ print("%-36s %.4f ms/step  stage1 %.4f ms (%.1f%%)  codes %.3f fin %.3f s2 %.3f 
     name or "(default)", d["ms_per_step"], d["roofline"]["kernel_ms"], 100 * d["roofline"]["frac"], st["codes"], st["finalize_fallback"],
     st["stage2_rows"], d.get("overlap", {}).get("ms_per_step", 0)))
 PY
+  rm -f "$log"
 done
 done

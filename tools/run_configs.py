@@ -55,7 +55,7 @@ def harness(tag, n, d, k, Q, reps, cpu_q, outdir):
 
 
 def bench(tag, extra, outdir):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + extra  # the lines carry the extras
     rc, txt, wall = run(cmd, os.path.join(outdir, "%s_bench.json.log" % tag))
     js = [l for l in txt.splitlines() if l.startswith("{")]
     line = json.loads(js[0]) if js else {}

@@ -4,7 +4,7 @@
 set -e
 out=${1:-gpurun_out/stage1_sq_counters.md}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-args="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-api --no-overlap-extra --data randn"
+args="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-api --no-overlap-extra --data randn"
 rm -rf gpurun_out/pmc_a gpurun_out/pmc_b
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/pmc_a -- python3 $args > gpurun_out/pmc_a.log 2>&1
 echo "pass A done"

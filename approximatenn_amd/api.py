@@ -312,6 +312,22 @@ class Index:
         """annhip_index_set_fixed: opt-in non-parity query mode (own hash codes, every candidate slot; include/ann_hip.h)."""
         self.lib.annhip_index_set_fixed(self.h, int(bool(on)))
 
+    ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
+
+    def set_rows(self, rows):
+        """annhip_index_set_rows: "f16" = opt-in binary16 point rows (results = the reference's on the rows rounded to
+        binary16; f32 index, all rows on this device), "native" = the rows as given (the default).  ValueError where the
+        library refuses (f64 index, resharded index, unknown value); the setting is then unchanged."""
+        code = self.ROWS.get(rows, rows) if isinstance(rows, str) else rows
+        if not isinstance(code, int) or self.lib.annhip_index_set_rows(self.h, code) != 0:
+            raise ValueError("annhip_index_set_rows refused rows=%r for this index (%s)" % (rows, self.prec))
+
+    @property
+    def rows(self):
+        """annhip_index_rows: "native" or "f16"."""
+        code = int(self.lib.annhip_index_rows(self.h))
+        return {v: k for k, v in self.ROWS.items()}.get(code, code)
+
     def workspace(self):
         """annhip_workspace_create: scratch for one in-flight batch (pass to query(ws=..., stream=...))."""
         ws = self.lib.annhip_workspace_create(self.h)

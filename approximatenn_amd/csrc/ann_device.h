@@ -25,6 +25,28 @@ typedef double2 VT;
 #define ANN_WAVE 64
 #define ANN_ID_NONE 0xFFFFFFFFu
 
+// Point-row storage of the query kernels (annhip_index_set_rows): RT = FT (native rows) or, in the f32 library only,
+// RH = IEEE binary16.  A chunk of ANN_VEC row elements is kept in registers as it was loaded (RowRaw<RT>::T: a 16-byte
+// VT, or 8 bytes of halves) and widened to VT only where it is reduced (raw_vt), so the loads of a prefetch ring stay in
+// flight.  The widening is exact: every binary16 value is a float.
+typedef _Float16 RH;
+typedef _Float16 rh4 __attribute__((ext_vector_type(4)));
+template <typename RT>
+struct RowRaw {
+  typedef VT T;
+};
+__device__ __forceinline__ VT raw_vt(VT v) { return v; }
+#ifdef USE_FLOAT
+template <>
+struct RowRaw<RH> {
+  typedef rh4 T;
+};
+__device__ __forceinline__ VT raw_vt(rh4 v) {
+  typedef float f4n __attribute__((ext_vector_type(4)));
+  return __builtin_bit_cast(VT, __builtin_convertvector(v, f4n));
+}
+#endif
+
 __device__ __forceinline__ UB ft_bits(FT x) { return __builtin_bit_cast(UB, x); }
 __device__ __forceinline__ FT ft_from_bits(UB b) { return __builtin_bit_cast(FT, b); }
 __device__ __forceinline__ FT ft_inf() {
@@ -247,14 +269,18 @@ enum { ROW_SQDIFF = 0, ROW_PRODUCT = 1 };
 // node because it turns -0 into +0 and the hash reads the raw sign bit (compute.cl:165-166,229).
 // The result is valid in lane position 0 of each LPR-lane group ONLY (the cross-lane levels pull the partner's
 // value downwards with DPP row shifts; the other lanes end up with partial sums nobody reads).
-template <int D, int MODE>
-__device__ __forceinline__ FT row_reduce(const VT (&a)[RowLay<D>::C], const VT (&b)[RowLay<D>::C]) {
+// b: the row's chunks as loaded (RowRaw), widened here.
+template <int D, int MODE, typename BR = VT>
+__device__ __forceinline__ FT row_reduce(const VT (&a)[RowLay<D>::C], const BR (&b)[RowLay<D>::C]) {
   typedef RowLay<D> L;
   FT e[L::C][ANN_VEC];
+  VT bv[L::C];
+#pragma unroll
+  for (int c = 0; c < L::C; c++) bv[c] = raw_vt(b[c]);
 #pragma unroll
   for (int c = 0; c < L::C; c++) {
     const FT *pa = reinterpret_cast<const FT *>(&a[c]);
-    const FT *pb = reinterpret_cast<const FT *>(&b[c]);
+    const FT *pb = reinterpret_cast<const FT *>(&bv[c]);
 #pragma unroll
     for (int j = 0; j < ANN_VEC; j++) {
       if (MODE == ROW_SQDIFF) {
@@ -413,13 +439,16 @@ __device__ __forceinline__ void oc_tail(FT (&e)[ANN_VEC], int p) {
   }
 }
 
-template <int C, int MODE, int OC = 0>
-__device__ __forceinline__ FT row_reduce_oc(const VT (&a)[C], const VT (&b)[C], int oc, int p, int s0 = 0) {  // s0 > 0: tree length (unaligned d)
+template <int C, int MODE, int OC = 0, typename BR = VT>
+__device__ __forceinline__ FT row_reduce_oc(const VT (&a)[C], const BR (&b)[C], int oc, int p, int s0 = 0) {  // s0 > 0: tree length (unaligned d)
   FT e[C][ANN_VEC];
+  VT bv[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) bv[c] = raw_vt(b[c]);
 #pragma unroll
   for (int c = 0; c < C; c++) {
     const FT *pa = reinterpret_cast<const FT *>(&a[c]);
-    const FT *pb = reinterpret_cast<const FT *>(&b[c]);
+    const FT *pb = reinterpret_cast<const FT *>(&bv[c]);
 #pragma unroll
     for (int j = 0; j < ANN_VEC; j++) {
       if (MODE == ROW_SQDIFF) {
@@ -464,17 +493,17 @@ __device__ __forceinline__ FT row_reduce_oc(const VT (&a)[C], const VT (&b)[C], 
 
 // Any d: the whole wave works on one row, staging the d terms in LDS scratch m[d] and running the
 // in-place tree literally (odd s term included).  a = left operand (LDS or global), b = row (global).
-// Returns the sum in every lane.
-template <int MODE>
-__device__ inline FT row_reduce_generic(int d, const FT *a, const FT *b, FT *m) {
+// Returns the sum in every lane.  b may be a row of halves (RH): each element is widened exactly before it is used.
+template <int MODE, typename BT = FT>
+__device__ inline FT row_reduce_generic(int d, const FT *a, const BT *b, FT *m) {
   const int lane = lane_id();
   const FT zero = 0;
   for (int z = lane; z < d; z += ANN_WAVE) {
     if (MODE == ROW_SQDIFF) {
-      FT df = a[z] - b[z];
+      FT df = a[z] - (FT)b[z];
       m[z] = df * df;
     } else {
-      m[z] = a[z] * b[z];
+      m[z] = a[z] * (FT)b[z];
     }
   }
   wave_lds_sync();

@@ -4,6 +4,7 @@
 // Reference being replaced: the OpenCL shim /root/reference/alggp.c (buffers, kernel launches) plus the
 // host orchestration /root/reference/alg.c as compiled for the GPU, and /root/reference/gpu_comp.c.
 // There is no CPU fallback anywhere in this file: without a HIP device every entry point exits loudly.
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -80,6 +81,8 @@ struct EnvCfg {
   int s2_multi = 1;     // ANN_HIP_S2_MULTI: 0 = sharded stage-2 distances with one workgroup per query (A/B of stage2_dist_multi_kernel)
   int codes_lpq = 1;    // ANN_HIP_CODES_LPQ: 0 = the lanes-per-row hash kernel for every row length (A/B)
   int tie = 1;          // ANN_HIP_TIE: 0 = flagged rows always take the literal network (no tie path, ann_tie.h)
+  int rows = 0;         // ANN_HIP_ROWS: f16 = query_gpu's resident single-device index reads binary16 rows (annhip_index_set_rows)
+  bool rows_warned = false;  // ... and the one warning where it cannot (f64 library, sharded modes) has been printed
 };
 static EnvCfg g_env;
 static size_t env_size(const char *name, size_t dflt) {
@@ -112,6 +115,8 @@ static void load_env() {
   c.codes_lpq = env_int("ANN_HIP_CODES_LPQ", 1);
   c.s2_multi = env_int("ANN_HIP_S2_MULTI", 1);
   c.fin_tail = env_int("ANN_HIP_FIN_TAIL", 1);
+  const char *rw = getenv("ANN_HIP_ROWS");
+  c.rows = rw && !strcmp(rw, "f16") ? ANNHIP_ROWS_F16 : ANNHIP_ROWS_NATIVE;
   const char *cm = getenv("ANN_HIP_CACHE");
   c.cache_mode = !cm ? 0 : !strcmp(cm, "strict") ? 1 : !strcmp(cm, "off") ? 2 : 0;
   g_env = c;
@@ -293,6 +298,8 @@ struct annhip_index {
   int gather_pieces = 1;  // annhip_sh_stage1 in this many launches (annhip_index_set_gather_pieces)
   int gather_slots = 0;   // annhip_sh_stage1 as a persistent grid holding this many waves per SIMD (0 = one workgroup per query)
   int fixed = 0;          // annhip_index_set_fixed: opt-in non-parity query mode (Q1/Q2 undone)
+  int rows = ANNHIP_ROWS_NATIVE;  // annhip_index_set_rows: which copy of the point rows the single-device query reads
+  RH *d_points_h = NULL;          // binary16 copy of the rows (made on the first ANNHIP_ROWS_F16, kept until destroy/reshard)
 };
 
 static QParams make_params(const annhip_index *ix) {
@@ -308,6 +315,13 @@ static QParams make_params(const annhip_index *ix) {
   P.q0 = 0, P.qn = 0;
   P.fixed = ix->fixed ? 1u : 0u;
   if (ix->fixed) P.P1 = P.Lc1 = P.L1;  // every slot of the candidate row takes part
+  return P;
+}
+
+// QParams of the single-device query path (annhip_query / _on / _slice, annhip_stream_*): the rows the index is set to
+static QParams query_params(const annhip_index *ix) {
+  QParams P = make_params(ix);
+  if (ix->rows == ANNHIP_ROWS_F16) P.points_h = ix->d_points_h;
   return P;
 }
 
@@ -396,6 +410,50 @@ extern "C" void annhip_index_set_gather_slots(annhip_index *ix, int waves_per_si
 }
 extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) { ix->fixed = fixed ? 1 : 0; }
 
+#ifdef USE_FLOAT
+// rows -> binary16, round to nearest even (overflow -> +-inf, subnormals kept, NaN stays NaN)
+__global__ void rows_to_half_kernel(size_t count, const float *__restrict__ in, __half *__restrict__ out) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
+    out[e] = __float2half_rn(in[e]);
+}
+#endif
+
+extern "C" int annhip_index_set_rows(annhip_index *ix, int rows) {
+  if (rows != ANNHIP_ROWS_NATIVE && rows != ANNHIP_ROWS_F16) {
+    fprintf(stderr, "annhip_index_set_rows: unknown row storage %d (ANNHIP_ROWS_NATIVE = 0, ANNHIP_ROWS_F16 = 1)\n", rows);
+    return -1;
+  }
+#ifndef USE_FLOAT
+  if (rows == ANNHIP_ROWS_F16) {
+    fprintf(stderr, "annhip_index_set_rows: binary16 rows are a feature of the f32 library only\n");
+    return -1;
+  }
+#else
+  if (rows == ANNHIP_ROWS_F16) {
+    if (!(ix->lo == 0 && ix->hi == ix->n)) {
+      fprintf(stderr, "annhip_index_set_rows: binary16 rows need the whole index on this device (rows [0, n))\n");
+      return -1;
+    }
+    if (!ix->d_points_h) {  // first enable: the copy is made on the device and kept (switching back and forth is free)
+      const size_t count = ix->n * ix->d;
+      ix->d_points_h = dev_alloc<RH>(count);
+      HIPCHECK(hipDeviceSynchronize());  // the native rows may have been written on another stream
+      rows_to_half_kernel<<<grid_for(count, 256, 1u << 20), 256>>>(count, ix->d_points, reinterpret_cast<__half *>(ix->d_points_h));
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipDeviceSynchronize());
+    }
+  }
+#endif
+  ix->rows = rows;
+  return 0;
+}
+extern "C" int annhip_index_rows(const annhip_index *ix) { return ix->rows; }
+static void drop_half_rows(annhip_index *ix) {
+  if (ix->d_points_h) HIPCHECK(hipFree(ix->d_points_h));
+  ix->d_points_h = NULL;
+  ix->rows = ANNHIP_ROWS_NATIVE;
+}
+
 extern "C" annhip_index *annhip_index_create(const save_t *save, const ftype *points, int on_device,
                                              size_t row_lo, size_t row_hi) {
   gpu_init();
@@ -445,6 +503,7 @@ extern "C" annhip_index *annhip_index_create(const save_t *save, const ftype *po
 extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points_dev, size_t row_lo, size_t row_hi) {
   if (row_lo > row_hi || row_hi > ix->n) die("bad row range");
   HIPCHECK(hipDeviceSynchronize());
+  drop_half_rows(ix);  // binary16 rows are for the whole index on one device: a resharded index reads native rows
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -457,6 +516,7 @@ extern "C" void annhip_index_destroy(annhip_index *ix) {
   if (!ix) return;
   HIPCHECK(hipDeviceSynchronize());
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
+  drop_half_rows(ix);
   for (u32 *t : ix->d_tabs)
     if (t) HIPCHECK(hipFree(t));
   for (uint2 *sg : ix->d_segs)
@@ -612,6 +672,16 @@ static bool layout_is_generic(int code) { return code == 0 || code == ANN_D_FOLD
 #else
 #define ANN_CASE_1024(CALL)
 #endif
+// The query kernels that read point rows come in two row types (QParams::points_h set: binary16 rows, f32 library only).
+#ifdef USE_FLOAT
+#define ANN_DISPATCH_ROWS(P, CALL_R, DD) \
+  do {                                   \
+    if ((P).points_h) CALL_R(DD, RH);    \
+    else CALL_R(DD, FT);                 \
+  } while (0)
+#else
+#define ANN_DISPATCH_ROWS(P, CALL_R, DD) CALL_R(DD, FT)
+#endif
 // kernels that know all three layouts (codes, stage 1, rows)
 #define ANN_DISPATCH_D(dval, CALL) ANN_DISPATCH_CODE(layout_code((size_t)(dval)), CALL)
 // kernels with the power-of-two and the generic layout only (bucket-centric precomp, recall)
@@ -761,27 +831,29 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   }
   // (Chaining the stage-1 launches of overlapping batches through an event was tried and is slower, 7.9 vs 8.3 M q/s:
   // letting consecutive gathers overlap is what hides the workgroup tail of each launch.)
-#define CALL_V(DD, SG, FU)                                                                                   \
+#define CALL_V(DD, SG, FU, RT)                                                                               \
   do {                                                                                                       \
-    allow_lds(stage1_select_kernel<DD, SG, FU>, smem);                                                       \
+    allow_lds(stage1_select_kernel<DD, SG, FU, RT>, smem);                                                   \
     const size_t np = (size_t)std::max(1, std::min(pieces, 64)), per = (Q + np - 1) / np;                    \
     for (size_t a = 0; a < Q; a += per) {                                                                    \
       QParams Pp = P;                                                                                        \
       Pp.q0 = (u32)a, Pp.qn = (u32)std::min(per, Q - a);                                                     \
-      hipLaunchKernelGGL((stage1_select_kernel<DD, SG, FU>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem, s, \
+      hipLaunchKernelGGL((stage1_select_kernel<DD, SG, FU, RT>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem, s, \
                          Pp, kq, y, alias, codes, K1, cap, runs_used, cand_d, cand_i, nvt, nvo, F, cand_key); \
     }                                                                                                        \
   } while (0)
-#define CALL(DD)                                 \
-  do {                                           \
-    if (use_seg == 2) CALL_V(DD, 2, false);                  \
-    else if (use_seg && F.enabled == 1) CALL_V(DD, 1, true);      \
-    else if (use_seg) CALL_V(DD, 1, false);                  \
-    else if (F.enabled == 1) CALL_V(DD, 0, true);                 \
-    else CALL_V(DD, 0, false);                               \
+#define CALL_R(DD, RT)                                       \
+  do {                                                       \
+    if (use_seg == 2) CALL_V(DD, 2, false, RT);              \
+    else if (use_seg && F.enabled == 1) CALL_V(DD, 1, true, RT); \
+    else if (use_seg) CALL_V(DD, 1, false, RT);              \
+    else if (F.enabled == 1) CALL_V(DD, 0, true, RT);        \
+    else CALL_V(DD, 0, false, RT);                           \
   } while (0)
+#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
   ANN_DISPATCH_D(P.d, CALL);
 #undef CALL
+#undef CALL_R
 #undef CALL_V
   HIPCHECK(hipGetLastError());
   if (prof) {
@@ -860,15 +932,17 @@ static void launch_rows(const QParams &P, size_t Q, const FT *y, int alias, cons
   // device-driven: a flat persistent grid over (row, part) items (see the kernel); otherwise one workgroup per (row, part)
   const unsigned flat = live_rows ? split : 0;
   const dim3 grid = live_rows ? dim3((unsigned)std::min<size_t>(nq * split, 512)) : dim3((unsigned)nq, split);
-#define CALL(DD)                                                                                         \
+#define CALL_R(DD, RT)                                                                                   \
   do {                                                                                                   \
-    allow_lds(row_dists_kernel<DD, MODE>, smem);                                                         \
-    hipLaunchKernelGGL((row_dists_kernel<DD, MODE>), grid, dim3(block), smem, s, P, kq, y,               \
+    allow_lds(row_dists_kernel<DD, MODE, RT>, smem);                                                     \
+    hipLaunchKernelGGL((row_dists_kernel<DD, MODE, RT>), grid, dim3(block), smem, s, P, kq, y,           \
                        alias, codes, qidx, xbase, len, top_i, top_d, ids, dist, rows_done, live_rows,        \
                        (u32)nq, chunk, live_off, flat);                                                      \
   } while (0)
+#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
   ANN_DISPATCH_D(P.d, CALL);
 #undef CALL
+#undef CALL_R
   HIPCHECK(hipGetLastError());
 }
 
@@ -935,14 +1009,16 @@ static void launch_stage2_fused(const QParams &P, size_t Q, const FT *y, int ali
   smem += sizeof(FT) * (size_t)P.Lc2;
   smem = (smem + 15) & ~(size_t)15;
   if (d_needs_lds_row(P.d)) smem += sizeof(FT) * (size_t)P.d * 3;
-#define CALL(DD)                                                                                                   \
+#define CALL_R(DD, RT)                                                                                             \
   do {                                                                                                             \
-    allow_lds((stage2_fused_kernel<DD, IdOut>), smem);                                                             \
-    hipLaunchKernelGGL((stage2_fused_kernel<DD, IdOut>), dim3((unsigned)nq), dim3(env().s2_threads), smem, s, P, (int)Q, y, alias, \
+    allow_lds((stage2_fused_kernel<DD, IdOut, RT>), smem);                                                         \
+    hipLaunchKernelGGL((stage2_fused_kernel<DD, IdOut, RT>), dim3((unsigned)nq), dim3(env().s2_threads), smem, s, P, (int)Q, y, alias, \
                        top_i, top_d, P.Lc2, out_ids, out_d, rows_ctr, xbase);                                      \
   } while (0)
+#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
   ANN_DISPATCH_D(P.d, CALL);
 #undef CALL
+#undef CALL_R
   HIPCHECK(hipGetLastError());
 }
 
@@ -966,19 +1042,21 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
   if ((u32)P.k >= P2 || smem > 150 * 1024 || nq > 64 * chunk) return false;
   u32 *fl = (u32 *)flist.need(sizeof(u32) * nq);
   zero_u32_kernel<<<1, 1, 0, s>>>(d_fcount);
-#define CALL_T(DD, TT, OUT)                                                                                         \
+#define CALL_T(DD, TT, OUT, RT)                                                                                     \
   do {                                                                                                              \
-    allow_lds((stage2_select_kernel<DD, TT>), smem);                                                                \
-    hipLaunchKernelGGL((stage2_select_kernel<DD, TT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias, \
+    allow_lds((stage2_select_kernel<DD, TT, RT>), smem);                                                            \
+    hipLaunchKernelGGL((stage2_select_kernel<DD, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias, \
                        top_i, top_d, P2, K1, cap, OUT, out_d, fl, d_fcount, exact_total, rows_ctr, xbase);          \
   } while (0)
-#define CALL(DD)                                   \
+#define CALL_R(DD, RT)                             \
   do {                                             \
-    if (out64) CALL_T(DD, size_t, out64);          \
-    else CALL_T(DD, u32, out32);                   \
+    if (out64) CALL_T(DD, size_t, out64, RT);      \
+    else CALL_T(DD, u32, out32, RT);               \
   } while (0)
+#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
   ANN_DISPATCH_D(P.d, CALL);
 #undef CALL
+#undef CALL_R
 #undef CALL_T
   HIPCHECK(hipGetLastError());
   if (P.fixed) return true;  // nothing is ever flagged: the selection IS the result
@@ -1094,7 +1172,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
                        size_t qstride = 0) {  // codes_ready: 1 = ws.codes holds the batch's codes, 2 = and ws.d_fcount has been reset
   if (!Q) return 0;
   if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
-  const QParams P = make_params(ix);
+  const QParams P = query_params(ix);
   if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
   const FT *y = reinterpret_cast<const FT *>(y_dev);
   const int k = P.k, K1 = k + 1;
@@ -2536,6 +2614,25 @@ static void query_single_end(annhip_index *ix, size_t ycnt, size_t *result, ftyp
             g_tmark[4] - g_tmark[3], g_tmark[5] - g_tmark[4]);
 }
 
+// ANN_HIP_ROWS before each query_gpu() step: the resident single-device index (ix; NULL = a sharded mode) is set to the
+// switch's row storage -- idempotent, so annhip_reload_env() takes effect on the next call.  Where binary16 rows do not
+// exist (f64 library, sharded modes) one warning per reading of the environment, and the rows stay native.
+static void env_rows_apply(annhip_index *ix) {
+  const int want = env().rows;
+  bool can = ix != NULL;
+#ifndef USE_FLOAT
+  can = false;
+#endif
+  if (want == ANNHIP_ROWS_F16 && !can) {
+    if (!g_env.rows_warned)
+      fprintf(stderr, "ANN_HIP_ROWS=f16: binary16 rows need the f32 library and one device (not ANN_HIP_DEVICES / "
+                      "ANN_HIP_VIRTUAL_SHARDS > 1); the rows stay native\n");
+    g_env.rows_warned = true;
+    return;
+  }
+  if (ix && annhip_index_set_rows(ix, want) != 0) die("ANN_HIP_ROWS: annhip_index_set_rows failed");
+}
+
 extern "C" size_t *query_gpu(const save_t *save, const ftype *points, size_t ycnt, const ftype *y,
                              ftype **dists_o) {
   RandGuard keep_callers_stream;
@@ -2567,6 +2664,7 @@ extern "C" size_t *query_gpu(const save_t *save, const ftype *points, size_t ycn
       if (hit >= 0) stale = fingerprint(save, points) != e.fp;
     };
     if (ycnt) {
+      env_rows_apply(e.ix);
       if (e.multi) {  // rows sharded over several devices (or virtual shards): the owner protocol, ann_multi_host.h
         multi_query(e.multi, ycnt, y, alias, result, dists, &verify);
       } else {

@@ -20,6 +20,8 @@
 //
 // Only slots below ann_need_len() are ever produced.
 #pragma once
+#include <type_traits>
+
 #include "ann_device.h"
 #include "ann_tie.h"
 
@@ -53,6 +55,8 @@ struct QParams {
                      // (grid == qn: one query per workgroup; a smaller, PERSISTENT grid leaves wave slots to other streams)
   u32 fixed;         // opt-in non-parity mode (annhip_index_set_fixed): a query reads ITS OWN codes (Q2 undone); the host
                      // also sets P1 = Lc1 = L1 (every slot is a candidate, Q1 undone) and no network decides an order
+  const RH *points_h = nullptr;  // the rows rounded to binary16 (annhip_index_set_rows; f32 library, whole index), or NULL:
+                                 // the kernels instantiated with RT = RH read these instead (the host dispatches on it)
 };
 
 #define ANN_S1_CHUNK 1024  // slots whose valid ids one wave stages in LDS at a time
@@ -78,21 +82,41 @@ __device__ __forceinline__ VT load_row_chunk(const VT *p) {
   }
 }
 
-// Chunk `ci` of a row of d elements in the layouts D < 0.  Aligned layouts: one 16-byte load (NT as above); the
-// unaligned one: element by element, zeros beyond d (never read by the tree, which starts at d).
-template <int D, bool NT>
-__device__ __forceinline__ VT oc_load_chunk(const FT *row, int ci, int d) {
+// The point rows the query kernels read: native (RT = FT) or binary16 (RT = RH, QParams::points_h).
+template <typename RT>
+__device__ __forceinline__ const RT *q_rows(const QParams &P) {
+  if constexpr (std::is_same<RT, FT>::value) return P.points;
+  else return P.points_h;
+}
+// Chunk `ci` (ANN_VEC elements) of an aligned row, as loaded: a 16-byte VT of native rows, or 8 bytes of 4 halves --
+// the same element-to-lane map either way, hence the same tree.
+template <typename RT, bool NT>
+__device__ __forceinline__ typename RowRaw<RT>::T load_row_raw(const RT *row, int ci) {
+  if constexpr (std::is_same<RT, FT>::value) {
+    return load_row_chunk<NT>(reinterpret_cast<const VT *>(row) + ci);
+  } else {
+    typedef typename RowRaw<RT>::T R;
+    const R *p = reinterpret_cast<const R *>(row) + ci;
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+  }
+}
+
+// Chunk `ci` of a row of d elements in the layouts D < 0.  Aligned layouts: one 16-byte load (NT as above; 8 bytes for a
+// row of halves); the unaligned one: element by element, zeros beyond d (never read by the tree, which starts at d).
+template <int D, bool NT, typename RT>
+__device__ __forceinline__ typename RowRaw<RT>::T oc_load_chunk(const RT *row, int ci, int d) {
   if constexpr (OcCode<D>::UA) {
-    VT v;
-    FT *o = reinterpret_cast<FT *>(&v);
+    typename RowRaw<RT>::T v;
+    RT *o = reinterpret_cast<RT *>(&v);
 #pragma unroll
     for (int j = 0; j < ANN_VEC; j++) {
       const int z = ci * ANN_VEC + j;
-      o[j] = z < d ? (NT ? __builtin_nontemporal_load(row + z) : row[z]) : (FT)0;
+      o[j] = z < d ? (NT ? __builtin_nontemporal_load(row + z) : row[z]) : (RT)0;
     }
     return v;
   } else {
-    return load_row_chunk<NT>(reinterpret_cast<const VT *>(row) + ci);
+    return load_row_raw<RT, NT>(row, ci);
   }
 }
 template <int D>
@@ -383,9 +407,10 @@ struct FoldPlan {
   }
 };
 
-template <int LV>
+template <int LV, typename RT>
 __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp, const u32 *list, int cnt, int alias, u32 x,
                                             const FT *yrow, SelState &S) {
+  const RT *rows = q_rows<RT>(P);
   constexpr int NL = 1 << LV;
   const int lane = lane_id(), d = P.d, sL = fp.sL, rpw = ANN_WAVE / sL;
   const int g = lane / sL, z = lane - g * sL;
@@ -410,11 +435,11 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
         for (int i = 0; i < (1 << l); i++) ax[(1 << l) + i] = yrow[fp.sprev[l] - 1 + off[i]];
       }
   }
-  FT bn[NL];
+  RT bn[NL];  // as loaded; widened where used
   u32 idn = 0;
   if (cnt > 0) {
     idn = list[(valid && g < cnt) ? g : 0];
-    const FT *rp = P.points + (size_t)(idn - P.lo) * d + z;
+    const RT *rp = rows + (size_t)(idn - P.lo) * d + z;
 #pragma unroll
     for (int i = 0; i < NL; i++) bn[i] = __builtin_nontemporal_load(rp + off[i]);
   }
@@ -422,7 +447,7 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
     FT e[NL];
 #pragma unroll
     for (int i = 0; i < NL; i++) {
-      const FT t = a[i] - bn[i];
+      const FT t = a[i] - (FT)bn[i];
       e[i] = t * t;
     }
     const u32 id = idn;
@@ -433,7 +458,7 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
     // left-overs of the odd levels: regular subtrees of the levels below, lane 0 of each group only.  (Loading them
     // with the row and computing them in every lane was tried: the extra VALU work costs more than the divergence.)
     if (z == 0) {
-      const FT *rp0 = P.points + (size_t)(id - P.lo) * d;
+      const RT *rp0 = rows + (size_t)(id - P.lo) * d;
 #pragma unroll
       for (int l = 0; l < LV; l++)
         if (fp.odd[l]) {
@@ -441,7 +466,7 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
 #pragma unroll
           for (int i = 0; i < NL; i++)
             if (i < (1 << l)) {
-              const FT df = ax[(1 << l) + i] - __builtin_nontemporal_load(rp0 + fp.sprev[l] - 1 + off[i]);
+              const FT df = ax[(1 << l) + i] - (FT)__builtin_nontemporal_load(rp0 + fp.sprev[l] - 1 + off[i]);
               t[i] = df * df;
             }
 #pragma unroll
@@ -455,7 +480,7 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
     const int nb = base + rpw;
     if (nb < cnt) {  // next pass in flight while this one is reduced
       idn = list[(valid && nb + g < cnt) ? nb + g : nb];
-      const FT *rp = P.points + (size_t)(idn - P.lo) * d + z;
+      const RT *rp = rows + (size_t)(idn - P.lo) * d + z;
 #pragma unroll
       for (int i = 0; i < NL; i++) bn[i] = __builtin_nontemporal_load(rp + off[i]);
     }
@@ -484,11 +509,13 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
 
 // B) gather the rows listed in list[0..cnt) (LDS), squared L2 to the query in the reference's tree order, keep
 // the keys that can still matter.  D > 0: LPR lanes per row, the next pass is prefetched while this one is reduced.
-template <int D>
+template <int D, typename RT = FT>
 __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list, int cnt, int alias, u32 x,
                                               const VT (&a)[RowChunks<D>::C],
                                               const FT *yq, FT *scratch, SelState &S, const FT *yrow = NULL) {
   const int lane = lane_id();
+  const RT *rows = q_rows<RT>(P);
+  typedef typename RowRaw<RT>::T RR;
   if constexpr (D > 0) {
     // PF row buffers per lane form a ring: while pass i is reduced, the loads of passes i+1 .. i+PF-1 are in flight
     // (each pass = RPW rows = 64 lanes x C x 16 B).  The loop is unrolled by PF so that every buffer has a fixed
@@ -496,7 +523,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
     typedef RowLay<D> L;
     constexpr int PF = ANN_S1_PREFETCH;
     const int p = lane % L::LPR, g = lane / L::LPR;
-    VT buf[PF][L::C];
+    RR buf[PF][L::C];
     u32 idb[PF];
 #pragma unroll
     for (int s = 0; s < PF; s++) {
@@ -504,9 +531,9 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
       idb[s] = 0;
       if (first < cnt) {
         idb[s] = list[first + g < cnt ? first + g : first];
-        const VT *rp = reinterpret_cast<const VT *>(P.points + (size_t)(idb[s] - P.lo) * D) + p;
+        const RT *rp = rows + (size_t)(idb[s] - P.lo) * D;
 #pragma unroll
-        for (int c = 0; c < L::C; c++) buf[s][c] = load_row_chunk<true>(rp + c * L::LPR);
+        for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
       }
     }
     for (int base = 0; base < cnt; base += PF * L::RPW) {
@@ -520,9 +547,9 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
           const int nb = cur + PF * L::RPW;
           if (nb < cnt) {
             idb[s] = list[nb + g < cnt ? nb + g : nb];
-            const VT *rp = reinterpret_cast<const VT *>(P.points + (size_t)(idb[s] - P.lo) * D) + p;
+            const RT *rp = rows + (size_t)(idb[s] - P.lo) * D;
 #pragma unroll
-            for (int c = 0; c < L::C; c++) buf[s][c] = load_row_chunk<true>(rp + c * L::LPR);
+            for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
           }
           const Key key = key_make(dist, id);
           const bool pass = act && p == 0 && key_less(key, S.tau);
@@ -537,7 +564,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
     }
   } else if constexpr (OcCode<D>::FOLD > 0) {  // the first tree levels inside a lane (host: layout_code chose this d for it)
     const FoldPlan fp(P.d);
-    gather_fold<OcCode<D>::FOLD>(P, fp, list, cnt, alias, x, yrow, S);
+    gather_fold<OcCode<D>::FOLD, RT>(P, fp, list, cnt, alias, x, yrow, S);
   } else if constexpr (D < 0 && !OcCode<D>::GEN) {
     // the same ring of PF row buffers as the power-of-two layout: passes i+1 .. i+PF-1 are in flight while pass i is
     // reduced (one pass = rpw rows of oc lanes x C chunks; d = 80: 12 rows = 3.8 KB).  With a single pass of lookahead
@@ -546,7 +573,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
     constexpr int PF = ANN_S1_PREFETCH_OC;
     const OcLanes<D> ol(P.d, lane);
     const int oc = ol.oc, rpw = ol.rpw, g = ol.g, p = ol.p;  // lanes with !ol.valid have no row
-    VT buf[PF][C];
+    RR buf[PF][C];
     u32 idb[PF];
 #pragma unroll
     for (int s = 0; s < PF; s++) {
@@ -554,7 +581,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
       idb[s] = 0;
       if (first < cnt) {
         idb[s] = list[(ol.valid && first + g < cnt) ? first + g : first];
-        const FT *rp = P.points + (size_t)(idb[s] - P.lo) * P.d;
+        const RT *rp = rows + (size_t)(idb[s] - P.lo) * P.d;
 #pragma unroll
         for (int c = 0; c < C; c++) buf[s][c] = oc_load_chunk<D, OcCode<D>::NT_ROWS>(rp, p + c * oc, P.d);
       }
@@ -570,7 +597,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
           const int nb = cur + PF * rpw;
           if (nb < cnt) {
             idb[s] = list[(ol.valid && nb + g < cnt) ? nb + g : nb];
-            const FT *rp = P.points + (size_t)(idb[s] - P.lo) * P.d;
+            const RT *rp = rows + (size_t)(idb[s] - P.lo) * P.d;
 #pragma unroll
             for (int c = 0; c < C; c++) buf[s][c] = oc_load_chunk<D, OcCode<D>::NT_ROWS>(rp, p + c * oc, P.d);
           }
@@ -589,7 +616,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
     for (int r = 0; r < cnt; r++) {
       const u32 id = list[r];
       if (alias && id == x) continue;  // wave-uniform
-      const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, P.points + (size_t)(id - P.lo) * P.d, scratch);
+      const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, rows + (size_t)(id - P.lo) * P.d, scratch);
       const Key key = key_make(dist, id);
       if (key_less(key, S.tau)) {  // wave-uniform
         if (lane == 0) S.kbuf[S.kcnt] = key;
@@ -606,12 +633,14 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
 // compute.cl:252-263); distances of the new slots gathered here (owned, valid, not the excluded self: else +inf);
 // the reference's network + rdups + network in LDS (alg.c:224-230); first k entries to out_ids/out_dist[x].
 // t_* and cnt2p are LDS scratch (len2 entries each; *cnt2p must be 0 on entry).  Returns the rows gathered.
-template <int D, typename IdOut>
+template <int D, typename IdOut, typename RT = FT>
 __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int alias, const VT (&a)[RowChunks<D>::C],
                                                    const FT *yq, FT *scratch, const Key *top, int k, u32 len2,
                                                    u32 *t_ids, u32 *t_slot, u32 *t_gid, FT *t_dist, u32 *cnt2p,
                                                    IdOut *__restrict__ out_ids, FT *__restrict__ out_dist) {
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
+  const RT *rows = q_rows<RT>(P);
+  typedef typename RowRaw<RT>::T RR;
   for (u32 j = threadIdx.x; j < len2; j += blockDim.x) {
     u32 id;
     if (j < (u32)k) {
@@ -641,15 +670,15 @@ __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int 
     constexpr int U = (ANN_ROWS_INFLIGHT / L::C) > 0 ? (ANN_ROWS_INFLIGHT / L::C) : 1;
     const int p = lane % L::LPR, g = lane / L::LPR;
     for (int base0 = w * L::RPW; base0 < cnt2; base0 += W * L::RPW * U) {
-      VT b[U][L::C];
+      RR b[U][L::C];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int r = base0 + u * W * L::RPW + g;
         if (base0 + u * W * L::RPW < cnt2) {  // wave-uniform: passes beyond the list are neither loaded nor reduced
           const u32 id = t_gid[r < cnt2 ? r : base0];
-          const VT *rp = reinterpret_cast<const VT *>(P.points + (size_t)(id - P.lo) * D) + p;
+          const RT *rp = rows + (size_t)(id - P.lo) * D;
 #pragma unroll
-          for (int c = 0; c < L::C; c++) b[u][c] = load_row_chunk<true>(rp + c * L::LPR);
+          for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
         }
       }
 #pragma unroll
@@ -667,13 +696,13 @@ __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int 
     const OcLanes<D> ol(P.d, lane);
     const int oc = ol.oc, rpw = ol.rpw, g = ol.g, p = ol.p;
     for (int base0 = w * rpw; base0 < cnt2; base0 += W * rpw * U) {
-      VT b[U][C];
+      RR b[U][C];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const int r = base0 + u * W * rpw + g;
         if (base0 + u * W * rpw < cnt2) {  // wave-uniform
           const u32 id = t_gid[(ol.valid && r < cnt2) ? r : base0];
-          const FT *rp = P.points + (size_t)(id - P.lo) * P.d;
+          const RT *rp = rows + (size_t)(id - P.lo) * P.d;
 #pragma unroll
           for (int c = 0; c < C; c++) b[u][c] = oc_load_chunk<D, OcCode<D>::NT_ROWS>(rp, p + c * oc, P.d);
         }
@@ -689,7 +718,7 @@ __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int 
     }
   } else {
     for (int r = w; r < cnt2; r += W) {
-      const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, P.points + (size_t)(t_gid[r] - P.lo) * P.d, scratch);
+      const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, rows + (size_t)(t_gid[r] - P.lo) * P.d, scratch);
       if (lane == 0) t_dist[t_slot[r]] = dist;
     }
   }
@@ -707,7 +736,7 @@ __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int 
 // launches and two round trips of the [Q][Lc2] rows through HBM (cfg3: 58 + 33 + 6 us -> one ~60 us kernel).
 // IdOut = size_t: query() results (the ABI's ids); u32: precomp's graph rows.  Query x = xbase + blockIdx.x; outputs are
 // indexed by x.
-template <int D, typename IdOut>
+template <int D, typename IdOut, typename RT>
 __global__ __launch_bounds__(128) void stage2_fused_kernel(QParams P, int Q, const FT *__restrict__ y, int alias,
                                                            const u32 *__restrict__ top_id, const FT *__restrict__ top_dist,
                                                            u32 len2, IdOut *__restrict__ out_ids,
@@ -743,7 +772,7 @@ __global__ __launch_bounds__(128) void stage2_fused_kernel(QParams P, int Q, con
     for (int c = 0; c < OcCode<D>::C; c++) a[c] = oc_load_chunk<D, false>(y + (size_t)x * P.d, ol.p + c * ol.oc, P.d);
   }
   __syncthreads();
-  const u32 got = stage2_in_workgroup<D, IdOut>(P, x, alias, a, yq, yq + (size_t)(1 + w) * P.d, top, k, len2, t_ids, t_slot,
+  const u32 got = stage2_in_workgroup<D, IdOut, RT>(P, x, alias, a, yq, yq + (size_t)(1 + w) * P.d, top, k, len2, t_ids, t_slot,
                                                 t_gid, t_dist, cnt2, out_ids, out_dist);
   if (rows_done && threadIdx.x == 0) atomicAdd(&rows_done[(x & 63u) * 8u], (unsigned long long)got);
 }
@@ -758,7 +787,7 @@ __global__ __launch_bounds__(128) void stage2_fused_kernel(QParams P, int Q, con
 // holds no +inf at all, which is the rule here -- k+1 keys were found: the duplicate test at P2-1 reads slot P2's id
 //  and can only ever kill the LARGEST entry of the prefix, which is among the first k outputs only if fewer
 // than k+1 distinct keys exist.  Everything else is appended to `flist` and takes the literal path afterwards.
-template <int D, typename IdOut>
+template <int D, typename IdOut, typename RT>
 __global__ __launch_bounds__(256) void stage2_select_kernel(QParams P, int Q, const FT *__restrict__ y, int alias,
                                                             const u32 *__restrict__ top_id, const FT *__restrict__ top_dist,
                                                             u32 P2, int K1, int cap, IdOut *__restrict__ out_ids,
@@ -837,13 +866,13 @@ __global__ __launch_bounds__(256) void stage2_select_kernel(QParams P, int Q, co
     if (cnt + ANN_WAVE > ANN_S1_CHUNK) {
       wave_lds_sync();
       vown += cnt;
-      gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+      gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
       cnt = 0;
     }
   }
   wave_lds_sync();
   vown += cnt;
-  gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
 
   {  // this wave's survivors -> merge buffer
     const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
@@ -912,7 +941,7 @@ struct FusedTail {
   FT *top_dist;
 };
 
-template <int D, int SEG, bool FUSED>  // SEG: 0 = slot scan, 1 = segment words + table rows, 2 = inline 32-byte records
+template <int D, int SEG, bool FUSED, typename RT>  // SEG: 0 = slot scan, 1 = segment words + table rows, 2 = inline 32-byte records
 __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, const FT *__restrict__ y,
                                                             int alias, const u32 *__restrict__ codes,
                                                             int K1, int cap, u32 runs_used,
@@ -1028,7 +1057,7 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
         if (lo < ANN_WAVE) {  // the next run does not fit any more: drain the list (a run is at most pm <= 255 ids)
           wave_lds_sync();
           vown += cnt;
-          gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+          gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
           cnt = 0;
         }
       }
@@ -1076,7 +1105,7 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
         if (cnt == ANN_S1_CHUNK) {
           wave_lds_sync();
           vown += cnt;
-          gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+          gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
           cnt = 0;
         }
       }
@@ -1103,14 +1132,14 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
       if (cnt + ANN_WAVE > ANN_S1_CHUNK) {
         wave_lds_sync();
         vown += cnt;
-        gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+        gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
         cnt = 0;
       }
     }
   }
   wave_lds_sync();
   vown += cnt;
-  gather_select<D>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  gather_select<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
 
   // ---- this wave's survivors -> merge buffer
   {
@@ -1195,7 +1224,7 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
   }
   // ---- fused stage 2 (det_results second half, alg.c:314-327) on this query's own workgroup
   {
-    const u32 cnt2 = stage2_in_workgroup<D, size_t>(P, x, alias, a, yq, scratch, kout_all /* wave 0's sorted survivors */,
+    const u32 cnt2 = stage2_in_workgroup<D, size_t, RT>(P, x, alias, a, yq, scratch, kout_all /* wave 0's sorted survivors */,
                                                     K1 - 1, F.len2, t_ids, t_slot, t_gid, t_dist, &cnts[2], F.out_ids, F.out_dist);
     if (threadIdx.x == 0) nv_own[x] = cnts[1] + cnt2;  // rows gathered for this query, both stages
   }
@@ -1416,7 +1445,7 @@ enum { MODE_TABLE = 0, MODE_GRAPH = 1, MODE_GRAPH_DIST = 2 };
 #define ANN_ID_FLAG 0xFFFFFFFEu  // top_id[x][0] of a query whose stage 1 has to be redone by the exact path
 #define ANN_RD_CHUNK 2048
 
-template <int D, int MODE>
+template <int D, int MODE, typename RT>
 __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const FT *__restrict__ y,
                                                         int alias, const u32 *__restrict__ codes,
                                                         const u32 *__restrict__ qidx, u32 xbase,
@@ -1428,6 +1457,8 @@ __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const 
                                                         const u32 *__restrict__ live_rows, u32 nrows,
                                                         u32 chunk, u32 live_off, u32 flat_split) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const RT *rows = q_rows<RT>(P);
+  typedef typename RowRaw<RT>::T RR;
   // Device-driven launches (live_rows != NULL) use a small persistent grid that walks the device-side row
   // count: launching one workgroup per POSSIBLE row just to exit cost ~50 us per launch at Q = 10k.
   // live_off: this launch covers entries [live_off, live_off + nrows) of the counted list (bounded workspace).
@@ -1525,15 +1556,15 @@ __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const 
       constexpr int U = (ANN_ROWS_INFLIGHT / L::C) > 0 ? (ANN_ROWS_INFLIGHT / L::C) : 1;  // row passes in flight (see stage2_in_workgroup)
       const int p = lane % L::LPR, g = lane / L::LPR;
       for (int base0 = w * L::RPW; base0 < cnt; base0 += W * L::RPW * U) {
-        VT b[U][L::C];
+        RR b[U][L::C];
 #pragma unroll
         for (int u = 0; u < U; u++) {
           const int r = base0 + u * W * L::RPW + g;
           if (base0 + u * W * L::RPW < cnt) {  // wave-uniform
             const u32 id = lid[r < cnt ? r : base0];
-            const VT *rp = reinterpret_cast<const VT *>(P.points + (size_t)(id - P.lo) * D) + p;
+            const RT *rp = rows + (size_t)(id - P.lo) * D;
 #pragma unroll
-            for (int c = 0; c < L::C; c++) b[u][c] = load_row_chunk<true>(rp + c * L::LPR);
+            for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
           }
         }
 #pragma unroll
@@ -1553,8 +1584,8 @@ __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const 
         const int r = base + g;
         const bool act = ol.valid && r < cnt;
         const u32 id = lid[act ? r : base];
-        const FT *rp = P.points + (size_t)(id - P.lo) * P.d;
-        VT b[C];
+        const RT *rp = rows + (size_t)(id - P.lo) * P.d;
+        RR b[C];
 #pragma unroll
         for (int c = 0; c < C; c++) b[c] = oc_load_chunk<D, OcCode<D>::NT_ROWS>(rp, p + c * oc, P.d);
         const FT dist = row_reduce_oc<C, ROW_SQDIFF, OC>(a, b, oc, p, oc_tree_len<D>(P.d));
@@ -1564,7 +1595,7 @@ __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const 
       FT *m = yq + (size_t)(1 + w) * P.d;
       for (int r = w; r < cnt; r += W) {
         const u32 id = lid[r];
-        const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, P.points + (size_t)(id - P.lo) * P.d, m);
+        const FT dist = row_reduce_generic<ROW_SQDIFF>(P.d, yq, rows + (size_t)(id - P.lo) * P.d, m);
         if (lane == 0) dist_row[lslot[r]] = dist;
       }
     }

@@ -49,6 +49,26 @@ void annhip_index_set_gather_slots(annhip_index *ix, int waves_per_simd);
  * candidates, stage 2 likewise; (n, +inf) where fewer than k exist.  Not comparable with the reference -- checked
  * against a brute force over the same candidate sets (tests/test_gpu_fixed_mode.py).  precomp is unaffected. */
 void annhip_index_set_fixed(annhip_index *ix, int fixed);
+/* Opt-in binary16 point rows (default ANNHIP_ROWS_NATIVE = the reference's results, bit for bit).  With ANNHIP_ROWS_F16,
+ * annhip_query / annhip_query_on / annhip_query_slice / annhip_stream_* on this index return exactly what the reference
+ * returns for query(save, h(P), y), where h(P) is the point matrix rounded to IEEE binary16 (round to nearest even;
+ * overflow -> +-inf, subnormals kept, NaN stays NaN) and widened back to float -- numpy's
+ * P.astype(np.float16).astype(np.float32).  Everything else is unchanged: save (built from the float rows), the queries,
+ * hashing, candidate slots, the reference's quirks, the network, rdups and the tie path; every distance is computed in
+ * float, in the reference's tree order, without FMA, from the exactly widened halves.  alias = 1 still excludes point x
+ * from query x.  A query moves half the row bytes (d = 128: 256 instead of 512 per candidate).
+ * The first enable converts the rows on the device into a copy owned by the index (n*d*2 bytes; the native rows stay
+ * where they are, so switching back is free and returns the old results bit for bit); annhip_index_destroy frees it.
+ * precomp is unaffected (it builds from the float rows), and so are fixed mode's inputs: set_fixed + ANNHIP_ROWS_F16 gives
+ * the exact top-k of the candidate sets on h(P).  Scope: the f32 library and a whole index on one device.  Returns 0, or
+ * -1 with one line on stderr for ANNHIP_ROWS_F16 in the f64 library, ANNHIP_ROWS_F16 on an index whose rows are not
+ * [0, n) (resharded), or an unknown value; ANNHIP_ROWS_NATIVE is accepted everywhere.  annhip_index_reshard returns the
+ * index to native rows and frees the copy; the annhip_sh_* staged calls always read the native rows.
+ * annhip_index_rows() = the current setting.  Drop-in path: ANN_HIP_ROWS=f16. */
+#define ANNHIP_ROWS_NATIVE 0
+#define ANNHIP_ROWS_F16 1
+int annhip_index_set_rows(annhip_index *ix, int rows);
+int annhip_index_rows(const annhip_index *ix);
 /* Point-shard an index that was built from all n rows: from now on this device owns rows [row_lo,row_hi) only
  * and reads them from shard_points_dev (device pointer to those rows, borrowed).  Tables and graph stay. */
 void annhip_index_reshard(annhip_index *ix, const ftype *shard_points_dev, size_t row_lo, size_t row_hi);

@@ -3,6 +3,9 @@
 // (1) grid-stride float4 read-reduce over 5 GiB, cached vs non-temporal loads, several grid sizes;
 // (2) pure random 512-byte-row gather with the stage-1 lane layout (8 lanes x 4 x 16 B per row, 8 rows per wave pass),
 //     ~14M rows like one cfg3 launch.  Measured round 1: stream 6.2 TB/s cached / 6.95 TB/s nt; gather 6.3 / 6.8 TB/s.
+// (3) random 320-byte rows (d = 80 float, static 5-lane layout);
+// (4) random 256-byte rows (d = 128 in binary16, annhip_index_set_rows): 8 lanes x 4 x 8 B per row -- the load form of the
+//     binary16 stage-1 kernel (same lane map as the float rows, chunks of 4 halves) -- and 8 lanes x 2 x 16 B per row.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,6 +62,25 @@ __global__ __launch_bounds__(256) void gather320(const v4 *p, size_t nrows, size
   }
   if (acc.x + acc.y + acc.z + acc.w == 12345.678f) out[0] = 1;
 }
+// random 256-byte rows, 8 lanes per row, C chunks of sizeof(V) bytes each: lane q takes chunks q, q+8, ... (the stage-1 map)
+template <typename V, int C, bool NT>
+__global__ __launch_bounds__(256) void gather256(const V *p, size_t nrows, size_t per_wave, float *out) {
+  const int lane = threadIdx.x & 63, g = lane >> 3, q = lane & 7;
+  size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  V acc = {};
+  unsigned long long h = wave * 0x9E3779B97F4A7C15ull + 12345;
+  for (size_t it = 0; it < per_wave; it++) {
+    h = h * 6364136223846793005ull + 1442695040888963407ull;
+    unsigned long long hh = h + g * 0xD1B54A32D192ED03ull;
+    hh ^= hh >> 29; hh *= 0xBF58476D1CE4E5B9ull; hh ^= hh >> 32;
+    size_t row = hh % nrows;
+    const V *rp = p + row * (8 * C) + q;
+#pragma unroll
+    for (int c = 0; c < C; c++) acc += NT ? __builtin_nontemporal_load(rp + c * 8) : rp[c * 8];
+  }
+  if (acc[0] + acc[1] == 12345.678f) out[0] = 1;
+}
+typedef float v2 __attribute__((ext_vector_type(2)));
 int main() {
   size_t bytes = (size_t)5120 << 20;  // 5 GiB, like the cfg3 point matrix
   v4 *p; float *out;
@@ -92,6 +114,18 @@ int main() {
     char nm[96];
     snprintf(nm, 96, "random 320B rows cached  %2d waves/CU", wpc); time([&] { gather320<false><<<blocks, 256>>>(p, nrows320, per_wave, out); }, nm, gb);
     snprintf(nm, 96, "random 320B rows nt      %2d waves/CU", wpc); time([&] { gather320<true><<<blocks, 256>>>(p, nrows320, per_wave, out); }, nm, gb);
+  }
+  size_t nrows256 = bytes / 256;
+  for (int wpc : {8, 16, 24, 32}) {
+    int blocks = 256 * wpc / 4; size_t waves = (size_t)blocks * 4, per_wave = 14000000 / 8 / waves + 1;
+    double gb = (double)waves * per_wave * 8 * 256 / 1e6;
+    char nm[96];
+    snprintf(nm, 96, "random 256B rows 4x8B  nt  %2d waves/CU", wpc);
+    time([&] { gather256<v2, 4, true><<<blocks, 256>>>(reinterpret_cast<const v2 *>(p), nrows256, per_wave, out); }, nm, gb);
+    snprintf(nm, 96, "random 256B rows 4x8B  cached %2d waves/CU", wpc);
+    time([&] { gather256<v2, 4, false><<<blocks, 256>>>(reinterpret_cast<const v2 *>(p), nrows256, per_wave, out); }, nm, gb);
+    snprintf(nm, 96, "random 256B rows 2x16B nt  %2d waves/CU", wpc);
+    time([&] { gather256<v4, 2, true><<<blocks, 256>>>(p, nrows256, per_wave, out); }, nm, gb);
   }
   return 0;
 }

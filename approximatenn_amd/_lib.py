@@ -58,6 +58,8 @@ def load(prec="f32"):
     lib = C.CDLL(path)
     vp, sz, u32p = C.c_void_p, C.c_size_t, C.c_void_p
     lib.annhip_precision.restype = C.c_char_p
+    lib.annhip_layout_code.restype = C.c_int
+    lib.annhip_layout_code.argtypes = [sz]
     lib.annhip_index_create.restype = vp
     lib.annhip_index_create.argtypes = [C.POINTER(SaveT), vp, C.c_int, sz, sz]
     lib.annhip_index_destroy.argtypes = [vp]
@@ -158,7 +160,7 @@ def load(prec="f32"):
 
 
 # every symbol include/*.h declares for the backend library (checked by tests/test_abi.py)
-EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp_gpu", "annhip_precision",
+EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp_gpu", "annhip_precision", "annhip_layout_code",
             "annhip_index_create", "annhip_index_destroy", "annhip_index_info", "annhip_index_set_stream", "annhip_index_set_gather_pieces", "annhip_index_set_gather_slots", "annhip_index_set_fixed",
             "annhip_index_set_rows", "annhip_index_rows",
             "annhip_index_export", "annhip_index_reshard", "annhip_save_write", "annhip_save_read", "annhip_precomp_index", "annhip_precomp_begin", "annhip_precomp_info", "annhip_precomp_init_merged", "annhip_precomp_hash",

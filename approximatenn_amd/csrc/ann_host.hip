@@ -579,13 +579,6 @@ extern "C" void annhip_index_export(const annhip_index *ix, save_t *save) {
 static int layout_code(size_t d, bool allow_oc = true) {
   if (d >= 16 && (d & (d - 1)) == 0 && d <= (sizeof(FT) == 4 ? 1024u : 512u)) return (int)d;
   bool static_oc = false;
-  {  // ANN_HIP_OC_C=c (experiment): the run-time-oc layout with c chunks per lane where d allows it (d = 96: 6 lanes x 4)
-    static const int force_c = env_int("ANN_HIP_OC_C", 0);
-    if (allow_oc && force_c > 0 && d % (ANN_VEC * (size_t)force_c) == 0) {
-      const size_t oc = d / (ANN_VEC * (size_t)force_c);
-      if (oc >= 2 && oc <= 64 && (force_c == 1 || force_c == 2 || force_c == 4 || force_c == 8)) return -force_c;
-    }
-  }
   if (allow_oc && d % ANN_VEC == 0) {
     size_t nc = d / ANN_VEC, C = 1;
     while (C < 8 && nc % (2 * C) == 0) C *= 2;
@@ -593,13 +586,11 @@ static int layout_code(size_t d, bool allow_oc = true) {
 #ifndef ANN_NO_STATIC_OC
     // 3 x 8 chunks as 6 lanes x 4 chunks, 5 x 8 as 10 x 4: half the registers per row buffer and twice as long
     // contiguous pieces per load instruction beat the lanes left idle (12 resp. 10 of the 16 lanes of a DPP row in use):
-    // d = 96 float 40.5 -> 61.1 % of the HBM peak in stage 1, d = 160 51.7 -> 69.0 % (N = 4M, Q = 10k; ANN_HIP_OC6=0: the
-    // 3- and 5-lane forms)
-    static const int oc6 = env_int("ANN_HIP_OC6", 1);
+    // d = 96 float 40.5 (3 lanes x 8) -> 61.1 % of the HBM peak in stage 1, d = 160 51.7 (5 x 8) -> 69.0 % (N = 4M, Q = 10k)
     // (5 x 4 chunks as 10 x 2 -- d = 80 float -- was measured too and loses: 52.2 % against 68.7 %)
-    if (oc6 && (oc == 3 || oc == 5) && C == 8) return -(int)(16 * (2 * oc) + 4);
+    if ((oc == 3 || oc == 5) && C == 8) return -(int)(16 * (2 * oc) + 4);
     if ((oc == 3 || oc == 5) && C >= 2) return -(int)(16 * oc + C);  // static layout, DPP-only tail (d = 80: oc = 5)
-    if (oc6 && (oc == 6 || oc == 10 || oc == 12) && C == 8) return -(int)(16 * oc + C);  // 3 x 16 / 5 x 16 / 3 x 32 chunks: d = 192 / 320 / 384 float
+    if ((oc == 6 || oc == 10 || oc == 12) && C == 8) return -(int)(16 * oc + C);  // 3 x 16 / 5 x 16 / 3 x 32 chunks: d = 192 / 320 / 384 float
 #endif
     static_oc = C > 2;  // many 16-byte chunks per lane: the aligned layout below beats the fold (d = 384: 4.0 vs 2.4 TB/s)
   }
@@ -636,56 +627,54 @@ static int layout_code(size_t d, bool allow_oc = true) {
   return 0;
 }
 static bool layout_is_generic(int code) { return code == 0 || code == ANN_D_FOLD4G || code == ANN_D_FOLD5G; }
-#define ANN_DISPATCH_CODE(code, CALL) \
-  switch (code) {                     \
-    case 16: CALL(16); break;         \
-    case 32: CALL(32); break;         \
-    case 64: CALL(64); break;         \
-    case 128: CALL(128); break;       \
-    case 256: CALL(256); break;       \
-    case 512: CALL(512); break;       \
-    ANN_CASE_1024(CALL)               \
-    case -1: CALL(-1); break;         \
-    case -2: CALL(-2); break;         \
-    case -4: CALL(-4); break;         \
-    case -8: CALL(-8); break;         \
-    case -50: CALL(-50); break;       \
-    case -52: CALL(-52); break;       \
-    case -56: CALL(-56); break;       \
-    case -82: CALL(-82); break;       \
-    case -84: CALL(-84); break;       \
-    case -88: CALL(-88); break;       \
-    case -100: CALL(-100); break;     \
-    case -104: CALL(-104); break;     \
-    case -164: CALL(-164); break;     \
-    case -168: CALL(-168); break;     \
-    case -200: CALL(-200); break;     \
-    case ANN_D_UNALIGNED: CALL(ANN_D_UNALIGNED); break; \
-    case ANN_D_FOLD2: CALL(ANN_D_FOLD2); break; \
-    case ANN_D_FOLD3: CALL(ANN_D_FOLD3); break; \
-    ANN_CASE_FOLD4(CALL) \
-    default: CALL(0); break;          \
-  }
-#define ANN_CASE_FOLD4(CALL) case ANN_D_FOLD4: CALL(ANN_D_FOLD4); break; case ANN_D_FOLD4G: CALL(ANN_D_FOLD4G); break; case ANN_D_FOLD5G: CALL(ANN_D_FOLD5G); break;
+
+// The layout table: the codes the launchers instantiate kernels for.  A new row layout is one entry in QueryLayouts
+// plus the case of layout_code() that returns it (its decoding lives in ann_device.h: RowLay / OcCode).
+template <int... Vs>
+struct Ints {};
+template <int... A, int... B>
+constexpr Ints<A..., B...> operator+(Ints<A...>, Ints<B...>) { return {}; }
+// what layout_code(d, false) returns -- bucket-centric precomp, sharded stage-2 distances, recall: the powers of two
+// (RowLay<D>; 4 KB rows in float only) and 0 (any d)
 #ifdef USE_FLOAT
-#define ANN_CASE_1024(CALL) case 1024: CALL(1024); break;
+typedef Ints<16, 32, 64, 128, 256, 512, 1024, 0> Pow2Layouts;
 #else
-#define ANN_CASE_1024(CALL)
+typedef Ints<16, 32, 64, 128, 256, 512, 0> Pow2Layouts;
 #endif
-// The query kernels that read point rows come in two row types (QParams::points_h set: binary16 rows, f32 library only).
+// what layout_code(d) returns -- the query path: those and the lanes-per-row codes -(16*OC + C), element-wise and folded
+typedef decltype(Pow2Layouts{} + Ints<-1, -2, -4, -8, -50, -52, -82, -84, -100, -104, -164, -168, -200, ANN_D_UNALIGNED,
+                                      ANN_D_FOLD2, ANN_D_FOLD3, ANN_D_FOLD4, ANN_D_FOLD4G, ANN_D_FOLD5G>{}) QueryLayouts;
+
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int... Vs>
+static bool in_table(Ints<Vs...>, int v) { return ((v == Vs) || ...); }
+// f(Int<V>{}) for the entry V == v: one instantiation of f per entry.  A value without an entry is a bug: it never
+// falls back to another layout's kernels.
+template <int... Vs, typename F>
+static void with_value(Ints<Vs...>, int v, F &&f) {
+  if (!((v == Vs && (f(Int<Vs>{}), true)) || ...)) die("no kernel instantiated for this layout code / template argument");
+}
+
+// The query kernels that read point rows come in two row types: f(TypeTag<RT>{}) with RT = RH (binary16) where
+// QParams::points_h is set -- f32 library only -- and FT otherwise.
+template <typename T>
+struct TypeTag {
+  typedef T type;
+};
+template <typename F>
+static void with_rows(const QParams &P, F &&f) {
 #ifdef USE_FLOAT
-#define ANN_DISPATCH_ROWS(P, CALL_R, DD) \
-  do {                                   \
-    if ((P).points_h) CALL_R(DD, RH);    \
-    else CALL_R(DD, FT);                 \
-  } while (0)
-#else
-#define ANN_DISPATCH_ROWS(P, CALL_R, DD) CALL_R(DD, FT)
+  if (P.points_h) return f(TypeTag<RH>{});
 #endif
-// kernels that know all three layouts (codes, stage 1, rows)
-#define ANN_DISPATCH_D(dval, CALL) ANN_DISPATCH_CODE(layout_code((size_t)(dval)), CALL)
-// kernels with the power-of-two and the generic layout only (bucket-centric precomp, recall)
-#define ANN_DISPATCH_D2(dval, CALL) ANN_DISPATCH_CODE(layout_code((size_t)(dval), false), CALL)
+  f(TypeTag<FT>{});
+}
+
+// the code the query launchers dispatch for d, looked up through the table (INT_MIN: none)
+extern "C" int annhip_layout_code(size_t d) {
+  const int code = layout_code(d);
+  return in_table(QueryLayouts{}, code) ? code : INT_MIN;
+}
 
 static bool d_is_fast(size_t d) { return layout_code(d, false) > 0; }   // power-of-two register layout
 static bool d_needs_lds_row(size_t d) { return layout_is_generic(layout_code(d)); }    // literal tree through LDS
@@ -695,23 +684,6 @@ static void allow_lds(K kernel, size_t bytes) {
   if (bytes > 160 * 1024) die("row too long for the LDS of one CU");
   if (bytes > 48 * 1024)
     HIPCHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
-template <int DD>
-static void launch_codes_lpq_d(const QParams &P, size_t Q, const FT *y, u32 *codes, hipStream_t s, u32 *zero_me, dim3 grid,
-                               size_t smem) {
-  if constexpr (DD > 0 && DD * sizeof(FT) <= 512) {
-    allow_lds(codes_lpq_kernel<DD>, smem);
-    hipLaunchKernelGGL(codes_lpq_kernel<DD>, grid, dim3(64 * ANN_LPQ_WAVES), smem, s, P, (int)Q, y, codes, zero_me);
-  }
-}
-
-template <int DD>
-static void launch_s2_multi_d(const QParams &P, size_t Q, const FT *y, int alias, u32 qpb, unsigned grid, const u32 *top_all,
-                              FT *dist_out, u32 *flagged, unsigned long long *rows_ctr, hipStream_t s) {
-  if constexpr (DD > 0)
-    hipLaunchKernelGGL(stage2_dist_multi_kernel<DD>, dim3(grid), dim3(256), 0, s, P, (int)Q, y, alias, P.Lc2, qpb, top_all,
-                       dist_out, flagged, rows_ctr);
 }
 
 // Qhash <= Q: only the first Qhash queries are hashed.  Stage 1 reads code[i*Q + x] for the tries i that own a
@@ -724,33 +696,33 @@ static void launch_codes(const QParams &P, size_t Qhash, const FT *y, u32 *codes
   if (d_is_fast(P.d) && (size_t)P.d * sizeof(FT) <= 512 && env().codes_lpq) {  // a lane per query (codes_lpq_kernel)
     const size_t smem = sizeof(FT) * ((size_t)P.ds + 1) * P.d + sizeof(u32) * ANN_WAVE * ANN_LPQ_WAVES;
     const dim3 grid((unsigned)((Q + ANN_WAVE - 1) / ANN_WAVE), (unsigned)P.T);
-#define CALL(DD) launch_codes_lpq_d<DD>(P, Q, y, codes, s, zero_me, grid, smem)
-    ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
+    with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D > 0 && D * sizeof(FT) <= 512) {
+        allow_lds(codes_lpq_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_lpq_kernel<D>, grid, dim3(64 * ANN_LPQ_WAVES), smem, s, P, (int)Q, y, codes, zero_me);
+      }
+    });
   } else if (d_is_fast(P.d)) {  // workgroup = (try, run of queries); the try's projection rows live in LDS
     const size_t smem = sizeof(FT) * (size_t)P.ds * P.d;
     const dim3 grid((unsigned)((Q + ANN_CODES_QPB - 1) / ANN_CODES_QPB), (unsigned)P.T);
-#define CALL(DD)                                                                                      \
-  do {                                                                                                \
-    if (DD > 0) {                                                                                     \
-      allow_lds(codes_kernel<DD>, smem);                                                              \
-      hipLaunchKernelGGL(codes_kernel<DD>, grid, dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me);       \
-    }                                                                                                 \
-  } while (0)
-    ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
+    with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D > 0) {
+        allow_lds(codes_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_kernel<D>, grid, dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me);
+      }
+    });
   } else {
     const unsigned grid = (unsigned)((items + wpb - 1) / wpb);
     const size_t smem = d_needs_lds_row(P.d) ? sizeof(FT) * wpb * 2 * (size_t)P.d : 0;
-#define CALL(DD)                                                                                      \
-  do {                                                                                                \
-    if (DD <= 0) {                                                                                    \
-      allow_lds(codes_kernel<(DD <= 0 ? DD : 0)>, smem);                                              \
-      hipLaunchKernelGGL(codes_kernel<(DD <= 0 ? DD : 0)>, dim3(grid), dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me); \
-    }                                                                                                 \
-  } while (0)
-    ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
+    with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D <= 0) {
+        allow_lds(codes_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_kernel<D>, dim3(grid), dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me);
+      }
+    });
   }
   HIPCHECK(hipGetLastError());
 }
@@ -831,30 +803,28 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   }
   // (Chaining the stage-1 launches of overlapping batches through an event was tried and is slower, 7.9 vs 8.3 M q/s:
   // letting consecutive gathers overlap is what hides the workgroup tail of each launch.)
-#define CALL_V(DD, SG, FU, RT)                                                                               \
-  do {                                                                                                       \
-    allow_lds(stage1_select_kernel<DD, SG, FU, RT>, smem);                                                   \
-    const size_t np = (size_t)std::max(1, std::min(pieces, 64)), per = (Q + np - 1) / np;                    \
-    for (size_t a = 0; a < Q; a += per) {                                                                    \
-      QParams Pp = P;                                                                                        \
-      Pp.q0 = (u32)a, Pp.qn = (u32)std::min(per, Q - a);                                                     \
-      hipLaunchKernelGGL((stage1_select_kernel<DD, SG, FU, RT>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem, s, \
-                         Pp, kq, y, alias, codes, K1, cap, runs_used, cand_d, cand_i, nvt, nvo, F, cand_key); \
-    }                                                                                                        \
-  } while (0)
-#define CALL_R(DD, RT)                                       \
-  do {                                                       \
-    if (use_seg == 2) CALL_V(DD, 2, false, RT);              \
-    else if (use_seg && F.enabled == 1) CALL_V(DD, 1, true, RT); \
-    else if (use_seg) CALL_V(DD, 1, false, RT);              \
-    else if (F.enabled == 1) CALL_V(DD, 0, true, RT);        \
-    else CALL_V(DD, 0, false, RT);                           \
-  } while (0)
-#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
-  ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
-#undef CALL_R
-#undef CALL_V
+  const size_t np = (size_t)std::max(1, std::min(pieces, 64)), per = (Q + np - 1) / np;
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      auto launch = [&](auto sg, auto fu) {
+        constexpr int D = decltype(dd)::value, SG = decltype(sg)::value;
+        constexpr bool FU = decltype(fu)::value;
+        using RT = typename decltype(rt)::type;
+        allow_lds(stage1_select_kernel<D, SG, FU, RT>, smem);
+        for (size_t a = 0; a < Q; a += per) {
+          QParams Pp = P;
+          Pp.q0 = (u32)a, Pp.qn = (u32)std::min(per, Q - a);
+          hipLaunchKernelGGL((stage1_select_kernel<D, SG, FU, RT>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem,
+                             s, Pp, kq, y, alias, codes, K1, cap, runs_used, cand_d, cand_i, nvt, nvo, F, cand_key);
+        }
+      };
+      if (use_seg == 2) launch(Int<2>{}, std::false_type{});
+      else if (use_seg && F.enabled == 1) launch(Int<1>{}, std::true_type{});
+      else if (use_seg) launch(Int<1>{}, std::false_type{});
+      else if (F.enabled == 1) launch(Int<0>{}, std::true_type{});
+      else launch(Int<0>{}, std::false_type{});
+    });
+  });
   HIPCHECK(hipGetLastError());
   if (prof) {
     HIPCHECK(hipEventRecord(ev.b, s));
@@ -863,22 +833,6 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
     if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
   }
   if (ix) ix->s1_launches += 1;
-}
-
-template <int DD>
-static void launch_bucket_d(const QParams &P, size_t nbuckets, int W, int K1, u32 list_cap, u32 mgroup, size_t smem, FT *cand_d,
-                            u32 *cand_i, u32 *nvt, u32 *nvo, hipStream_t s, u32 brem, u32 bmod) {
-  if constexpr (DD > 0) {
-    if (K1 <= ANN_WAVE) {
-      allow_lds((stage1_bucket_kernel<DD, false>), smem);
-      hipLaunchKernelGGL((stage1_bucket_kernel<DD, false>), dim3((unsigned)nbuckets), dim3(64 * W), smem, s, P, K1, list_cap,
-                         mgroup, cand_d, cand_i, nvt, nvo, brem, bmod);
-    } else {
-      allow_lds((stage1_bucket_kernel<DD, true>), smem);
-      hipLaunchKernelGGL((stage1_bucket_kernel<DD, true>), dim3((unsigned)nbuckets), dim3(64 * W), smem, s, P, K1, list_cap,
-                         mgroup, cand_d, cand_i, nvt, nvo, brem, bmod);
-    }
-  }
 }
 
 // bucket-centric stage 1 of precomp: returns false when the shape does not fit (caller uses the per-point kernel)
@@ -899,9 +853,19 @@ static bool launch_stage1_bucket(const QParams &P, const TryInfo &one, size_t nb
   if (env().bk_group) mgroup = (u32)std::min<size_t>(mgroup, std::max<size_t>(env().bk_group, (size_t)W));
   const size_t smem = fixed + sizeof(Key) * (size_t)mgroup * K1;
   if ((u32)P.k > P.P1) return false;
-#define CALL(DD) launch_bucket_d<DD>(P, nbuckets, W, K1, list_cap, mgroup, smem, cand_d, cand_i, nvt, nvo, s, brem, bmod)
-  ANN_DISPATCH_D2(P.d, CALL);
-#undef CALL
+  with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    if constexpr (D > 0) {
+      auto launch = [&](auto hi) {
+        constexpr bool HI = decltype(hi)::value;
+        allow_lds((stage1_bucket_kernel<D, HI>), smem);
+        hipLaunchKernelGGL((stage1_bucket_kernel<D, HI>), dim3((unsigned)nbuckets), dim3(64 * W), smem, s, P, K1, list_cap,
+                           mgroup, cand_d, cand_i, nvt, nvo, brem, bmod);
+      };
+      if (K1 <= ANN_WAVE) launch(std::false_type{});
+      else launch(std::true_type{});
+    }
+  });
   HIPCHECK(hipGetLastError());
   return true;
 }
@@ -932,17 +896,15 @@ static void launch_rows(const QParams &P, size_t Q, const FT *y, int alias, cons
   // device-driven: a flat persistent grid over (row, part) items (see the kernel); otherwise one workgroup per (row, part)
   const unsigned flat = live_rows ? split : 0;
   const dim3 grid = live_rows ? dim3((unsigned)std::min<size_t>(nq * split, 512)) : dim3((unsigned)nq, split);
-#define CALL_R(DD, RT)                                                                                   \
-  do {                                                                                                   \
-    allow_lds(row_dists_kernel<DD, MODE, RT>, smem);                                                     \
-    hipLaunchKernelGGL((row_dists_kernel<DD, MODE, RT>), grid, dim3(block), smem, s, P, kq, y,           \
-                       alias, codes, qidx, xbase, len, top_i, top_d, ids, dist, rows_done, live_rows,        \
-                       (u32)nq, chunk, live_off, flat);                                                      \
-  } while (0)
-#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
-  ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
-#undef CALL_R
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      constexpr int D = decltype(dd)::value;
+      using RT = typename decltype(rt)::type;
+      allow_lds(row_dists_kernel<D, MODE, RT>, smem);
+      hipLaunchKernelGGL((row_dists_kernel<D, MODE, RT>), grid, dim3(block), smem, s, P, kq, y, alias, codes, qidx, xbase, len,
+                         top_i, top_d, ids, dist, rows_done, live_rows, (u32)nq, chunk, live_off, flat);
+    });
+  });
   HIPCHECK(hipGetLastError());
 }
 
@@ -979,23 +941,17 @@ static void launch_exact_select(u32 L, u32 len, u32 in_stride, int k, size_t nq,
   if (tie_smem > 150 * 1024) nw = 0;
   if (!nw) tie = TieArgs{NULL, NULL, 0, NULL, 0}, tie_smem = 0;
   const size_t smem = std::max(in_lds ? row_smem : (size_t)0, tie_smem);
-#define CALL(LDS, NW)                                                                                                  \
-  do {                                                                                                                 \
-    allow_lds((exact_select_kernel<LDS, NW>), smem);                                                                   \
-    hipLaunchKernelGGL((exact_select_kernel<LDS, NW>), dim3(grid), dim3(block), smem, s, L, len, in_stride, k, ids,    \
-                       dist, qidx, xbase, out_i, out_d, ostride, ooff, live_rows, (u32)nq, out64, live_off, tie);      \
-  } while (0)
-#define CALL_NW(LDS)             \
-  do {                           \
-    if (nw == 0) CALL(LDS, 0);   \
-    else if (nw == 1) CALL(LDS, 1); \
-    else if (nw == 2) CALL(LDS, 2); \
-    else CALL(LDS, 4);           \
-  } while (0)
-  if (in_lds) CALL_NW(true);
-  else CALL_NW(false);
-#undef CALL_NW
-#undef CALL
+  auto launch = [&](auto lds, auto nwc) {
+    constexpr bool LDS = decltype(lds)::value;
+    constexpr int NW = decltype(nwc)::value;
+    allow_lds((exact_select_kernel<LDS, NW>), smem);
+    hipLaunchKernelGGL((exact_select_kernel<LDS, NW>), dim3(grid), dim3(block), smem, s, L, len, in_stride, k, ids, dist, qidx,
+                       xbase, out_i, out_d, ostride, ooff, live_rows, (u32)nq, out64, live_off, tie);
+  };
+  with_value(Ints<0, 1, 2, 4>{}, nw, [&](auto nwc) {
+    if (in_lds) launch(std::true_type{}, nwc);
+    else launch(std::false_type{}, nwc);
+  });
   HIPCHECK(hipGetLastError());
 }
 
@@ -1009,16 +965,15 @@ static void launch_stage2_fused(const QParams &P, size_t Q, const FT *y, int ali
   smem += sizeof(FT) * (size_t)P.Lc2;
   smem = (smem + 15) & ~(size_t)15;
   if (d_needs_lds_row(P.d)) smem += sizeof(FT) * (size_t)P.d * 3;
-#define CALL_R(DD, RT)                                                                                             \
-  do {                                                                                                             \
-    allow_lds((stage2_fused_kernel<DD, IdOut, RT>), smem);                                                         \
-    hipLaunchKernelGGL((stage2_fused_kernel<DD, IdOut, RT>), dim3((unsigned)nq), dim3(env().s2_threads), smem, s, P, (int)Q, y, alias, \
-                       top_i, top_d, P.Lc2, out_ids, out_d, rows_ctr, xbase);                                      \
-  } while (0)
-#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
-  ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
-#undef CALL_R
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      constexpr int D = decltype(dd)::value;
+      using RT = typename decltype(rt)::type;
+      allow_lds((stage2_fused_kernel<D, IdOut, RT>), smem);
+      hipLaunchKernelGGL((stage2_fused_kernel<D, IdOut, RT>), dim3((unsigned)nq), dim3(env().s2_threads), smem, s, P, (int)Q, y,
+                         alias, top_i, top_d, P.Lc2, out_ids, out_d, rows_ctr, xbase);
+    });
+  });
   HIPCHECK(hipGetLastError());
 }
 
@@ -1042,22 +997,20 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
   if ((u32)P.k >= P2 || smem > 150 * 1024 || nq > 64 * chunk) return false;
   u32 *fl = (u32 *)flist.need(sizeof(u32) * nq);
   zero_u32_kernel<<<1, 1, 0, s>>>(d_fcount);
-#define CALL_T(DD, TT, OUT, RT)                                                                                     \
-  do {                                                                                                              \
-    allow_lds((stage2_select_kernel<DD, TT, RT>), smem);                                                            \
-    hipLaunchKernelGGL((stage2_select_kernel<DD, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias, \
-                       top_i, top_d, P2, K1, cap, OUT, out_d, fl, d_fcount, exact_total, rows_ctr, xbase);          \
-  } while (0)
-#define CALL_R(DD, RT)                             \
-  do {                                             \
-    if (out64) CALL_T(DD, size_t, out64, RT);      \
-    else CALL_T(DD, u32, out32, RT);               \
-  } while (0)
-#define CALL(DD) ANN_DISPATCH_ROWS(P, CALL_R, DD)
-  ANN_DISPATCH_D(P.d, CALL);
-#undef CALL
-#undef CALL_R
-#undef CALL_T
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      auto launch = [&](auto *out) {  // the id type of the output rows: size_t (query()) or u32 (precomp's graph)
+        constexpr int D = decltype(dd)::value;
+        using RT = typename decltype(rt)::type;
+        using TT = std::remove_pointer_t<decltype(out)>;
+        allow_lds((stage2_select_kernel<D, TT, RT>), smem);
+        hipLaunchKernelGGL((stage2_select_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
+                           top_i, top_d, P2, K1, cap, out, out_d, fl, d_fcount, exact_total, rows_ctr, xbase);
+      };
+      if (out64) launch(out64);
+      else launch(out32);
+    });
+  });
   HIPCHECK(hipGetLastError());
   if (P.fixed) return true;  // nothing is ever flagged: the selection IS the result
   const size_t R = std::min(nq, chunk);
@@ -1585,10 +1538,13 @@ extern "C" void annhip_sh_stage2(annhip_index *ix, void *hip_stream, size_t Q, c
     u32 qpb = (u32)std::min<double>(64.0, std::max(1.0, 128.0 / (own * per)));
     qpb = std::max<u32>(1, std::min<u32>(qpb, ANN_S2M_CAP / per));
     const unsigned grid = (unsigned)((Q + qpb - 1) / qpb);
-#define CALL(DD) launch_s2_multi_d<DD>(P, Q, reinterpret_cast<const FT *>(y_dev), alias, qpb, grid, top_id_all_dev, \
-                                       reinterpret_cast<FT *>(dist_out_dev), flagged_dev, ix->profile == 1 ? ix->d_rows + 8 : NULL, s)
-    ANN_DISPATCH_D2(P.d, CALL);
-#undef CALL
+    with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D > 0)
+        hipLaunchKernelGGL(stage2_dist_multi_kernel<D>, dim3(grid), dim3(256), 0, s, P, (int)Q, reinterpret_cast<const FT *>(y_dev),
+                           alias, P.Lc2, qpb, top_id_all_dev, reinterpret_cast<FT *>(dist_out_dev), flagged_dev,
+                           ix->profile == 1 ? ix->d_rows + 8 : NULL);
+    });
     HIPCHECK(hipGetLastError());
     return;
   }
@@ -1750,17 +1706,15 @@ extern "C" void annhip_recall_ranks(size_t n, size_t d, size_t k, const ftype *p
   unsigned qgroups = (unsigned)std::min<size_t>((Q + wpb - 1) / wpb, tiles < 2048 ? (4096 / (tiles ? tiles : 1)) + 1 : 1);
   if (qgroups < 1) qgroups = 1;
   if (qgroups > 65535) qgroups = 65535;
-#define CALL(DD)                                                                                                  \
-  do {                                                                                                            \
-    allow_lds(recall_guess_dist_kernel<DD>, smem_g);                                                              \
-    hipLaunchKernelGGL(recall_guess_dist_kernel<DD>, dim3((unsigned)((Q + wpb - 1) / wpb)), dim3(64 * wpb), smem_g, 0, \
-                       pts, (u32)n, (int)d, (int)Q, (int)k, y, guess_dev, gd);                                   \
-    allow_lds(recall_scan_kernel<DD>, smem_s);                                                                    \
-    hipLaunchKernelGGL(recall_scan_kernel<DD>, dim3(tiles, qgroups), dim3(64 * wpb), smem_s, 0, pts, (u32)n, (int)d, \
-                       (int)Q, (int)k, y, gd, self, hist);                                                        \
-  } while (0)
-  ANN_DISPATCH_D2((int)d, CALL);
-#undef CALL
+  with_value(Pow2Layouts{}, layout_code(d, false), [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    allow_lds(recall_guess_dist_kernel<D>, smem_g);
+    hipLaunchKernelGGL(recall_guess_dist_kernel<D>, dim3((unsigned)((Q + wpb - 1) / wpb)), dim3(64 * wpb), smem_g, 0, pts, (u32)n,
+                       (int)d, (int)Q, (int)k, y, guess_dev, gd);
+    allow_lds(recall_scan_kernel<D>, smem_s);
+    hipLaunchKernelGGL(recall_scan_kernel<D>, dim3(tiles, qgroups), dim3(64 * wpb), smem_s, 0, pts, (u32)n, (int)d, (int)Q,
+                       (int)k, y, gd, self, hist);
+  });
   HIPCHECK(hipGetLastError());
   // rank[j] = #points closer than guess j = sum of hist[c] over the c's whose point is closer than gdist[j]:
   // a point counted in bin c has exactly c guesses at least as close as itself, so it is closer than guess j iff

@@ -21,6 +21,10 @@ typedef struct annhip_index annhip_index;
 
 /* "f32" or "f64": the precision this library was built for (ftype.h). */
 const char *annhip_precision(void);
+/* The row-layout code the query kernels are dispatched with for rows of d elements, looked up through the library's
+ * layout table (positive: power of two; negative: lanes-per-row / element-wise / folded forms; 0: any d), or INT_MIN
+ * if the table has no entry for it.  Host only: needs no device. */
+int annhip_layout_code(size_t d);
 
 /* ---- index lifecycle ------------------------------------------------------------------------- */
 /* Upload an index.  `points` holds rows [row_lo,row_hi) only (row-major, save->d_long each): the rows

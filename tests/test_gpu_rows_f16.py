@@ -60,7 +60,8 @@ def _same(got, want, what):
     assert bits_equal(dd, want[1]), "%s: distances not bit-identical" % what
 
 
-# d -> the layout code layout_code() picks in the f32 library (approximatenn_amd/csrc/ann_host.hip)
+# d -> the layout code layout_code() picks in the f32 library (approximatenn_amd/csrc/ann_host.hip; pinned by
+# tests/test_layout_table.py)
 LAYOUTS = [
     (128, "128: power of two"),
     (80, "-84: static 5 lanes x 4 chunks"),

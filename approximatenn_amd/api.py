@@ -313,20 +313,23 @@ class Index:
         self.lib.annhip_index_set_fixed(self.h, int(bool(on)))
 
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
+    # the names an index of each precision knows: every library serves its own narrow row type (ANNHIP_ROWS_F32 = 2)
+    ROWS_BY_PREC = {"f32": ROWS, "f64": {"native": 0, "f32": 2}}
 
     def set_rows(self, rows):
-        """annhip_index_set_rows: "f16" = opt-in binary16 point rows (results = the reference's on the rows rounded to
-        binary16; f32 index, all rows on this device), "native" = the rows as given (the default).  ValueError where the
-        library refuses (f64 index, resharded index, unknown value); the setting is then unchanged."""
-        code = self.ROWS.get(rows, rows) if isinstance(rows, str) else rows
+        """annhip_index_set_rows: opt-in narrow point rows -- "f16" (binary16) on an f32 index, "f32" (binary32) on an
+        f64 index: results = the reference's on the rows rounded to that type; all rows on this device.  "native" = the
+        rows as given (the default).  ValueError for a name this index's precision does not know and where the library
+        refuses (the other library's type, resharded index, unknown value); the setting is then unchanged."""
+        code = self.ROWS_BY_PREC[self.prec].get(rows) if isinstance(rows, str) else rows
         if not isinstance(code, int) or self.lib.annhip_index_set_rows(self.h, code) != 0:
             raise ValueError("annhip_index_set_rows refused rows=%r for this index (%s)" % (rows, self.prec))
 
     @property
     def rows(self):
-        """annhip_index_rows: "native" or "f16"."""
+        """annhip_index_rows: "native", or the narrow type of this index's precision ("f16" / "f32")."""
         code = int(self.lib.annhip_index_rows(self.h))
-        return {v: k for k, v in self.ROWS.items()}.get(code, code)
+        return {v: k for k, v in self.ROWS_BY_PREC[self.prec].items()}.get(code, code)
 
     def workspace(self):
         """annhip_workspace_create: scratch for one in-flight batch (pass to query(ws=..., stream=...))."""

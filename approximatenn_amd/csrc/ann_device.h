@@ -25,27 +25,33 @@ typedef double2 VT;
 #define ANN_WAVE 64
 #define ANN_ID_NONE 0xFFFFFFFFu
 
-// Point-row storage of the query kernels (annhip_index_set_rows): RT = FT (native rows) or, in the f32 library only,
-// RH = IEEE binary16.  A chunk of ANN_VEC row elements is kept in registers as it was loaded (RowRaw<RT>::T: a 16-byte
-// VT, or 8 bytes of halves) and widened to VT only where it is reduced (raw_vt), so the loads of a prefetch ring stay in
-// flight.  The widening is exact: every binary16 value is a float.
+// Point-row storage of the query kernels (annhip_index_set_rows): RT = FT (native rows) or RN, the library's narrow row
+// type: RH = IEEE binary16 in the f32 library, IEEE binary32 in the f64 library.  A chunk of ANN_VEC row elements is kept
+// in registers as it was loaded (RowRaw<RT>::T: a 16-byte VT, or 8 bytes of 4 halves / 2 floats) and widened to VT only
+// where it is reduced (raw_vt), so the loads of a prefetch ring stay in flight.  The widening is exact: every binary16
+// value is a float, every float a double.
 typedef _Float16 RH;
 typedef _Float16 rh4 __attribute__((ext_vector_type(4)));
+typedef float rf2 __attribute__((ext_vector_type(2)));
+#ifdef USE_FLOAT
+typedef RH RN;
+typedef rh4 RNV;  // ANN_VEC narrow elements
+typedef float ftn __attribute__((ext_vector_type(ANN_VEC)));
+#else
+typedef float RN;
+typedef rf2 RNV;
+typedef double ftn __attribute__((ext_vector_type(ANN_VEC)));
+#endif
 template <typename RT>
 struct RowRaw {
   typedef VT T;
 };
 __device__ __forceinline__ VT raw_vt(VT v) { return v; }
-#ifdef USE_FLOAT
 template <>
-struct RowRaw<RH> {
-  typedef rh4 T;
+struct RowRaw<RN> {
+  typedef RNV T;
 };
-__device__ __forceinline__ VT raw_vt(rh4 v) {
-  typedef float f4n __attribute__((ext_vector_type(4)));
-  return __builtin_bit_cast(VT, __builtin_convertvector(v, f4n));
-}
-#endif
+__device__ __forceinline__ VT raw_vt(RNV v) { return __builtin_bit_cast(VT, __builtin_convertvector(v, ftn)); }
 
 __device__ __forceinline__ UB ft_bits(FT x) { return __builtin_bit_cast(UB, x); }
 __device__ __forceinline__ FT ft_from_bits(UB b) { return __builtin_bit_cast(FT, b); }
@@ -493,7 +499,7 @@ __device__ __forceinline__ FT row_reduce_oc(const VT (&a)[C], const BR (&b)[C], 
 
 // Any d: the whole wave works on one row, staging the d terms in LDS scratch m[d] and running the
 // in-place tree literally (odd s term included).  a = left operand (LDS or global), b = row (global).
-// Returns the sum in every lane.  b may be a row of halves (RH): each element is widened exactly before it is used.
+// Returns the sum in every lane.  b may be a row of the narrow type (RN): each element is widened exactly before it is used.
 template <int MODE, typename BT = FT>
 __device__ inline FT row_reduce_generic(int d, const FT *a, const BT *b, FT *m) {
   const int lane = lane_id();

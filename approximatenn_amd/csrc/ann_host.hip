@@ -81,8 +81,8 @@ struct EnvCfg {
   int s2_multi = 1;     // ANN_HIP_S2_MULTI: 0 = sharded stage-2 distances with one workgroup per query (A/B of stage2_dist_multi_kernel)
   int codes_lpq = 1;    // ANN_HIP_CODES_LPQ: 0 = the lanes-per-row hash kernel for every row length (A/B)
   int tie = 1;          // ANN_HIP_TIE: 0 = flagged rows always take the literal network (no tie path, ann_tie.h)
-  int rows = 0;         // ANN_HIP_ROWS: f16 = query_gpu's resident single-device index reads binary16 rows (annhip_index_set_rows)
-  bool rows_warned = false;  // ... and the one warning where it cannot (f64 library, sharded modes) has been printed
+  int rows = 0;         // ANN_HIP_ROWS: f16 / f32 = query_gpu's resident single-device index reads narrow rows (annhip_index_set_rows)
+  bool rows_warned = false;  // ... and the one warning where it cannot (the other library's type, sharded modes) has been printed
 };
 static EnvCfg g_env;
 static size_t env_size(const char *name, size_t dflt) {
@@ -116,7 +116,7 @@ static void load_env() {
   c.s2_multi = env_int("ANN_HIP_S2_MULTI", 1);
   c.fin_tail = env_int("ANN_HIP_FIN_TAIL", 1);
   const char *rw = getenv("ANN_HIP_ROWS");
-  c.rows = rw && !strcmp(rw, "f16") ? ANNHIP_ROWS_F16 : ANNHIP_ROWS_NATIVE;
+  c.rows = !rw ? ANNHIP_ROWS_NATIVE : !strcmp(rw, "f16") ? ANNHIP_ROWS_F16 : !strcmp(rw, "f32") ? ANNHIP_ROWS_F32 : ANNHIP_ROWS_NATIVE;
   const char *cm = getenv("ANN_HIP_CACHE");
   c.cache_mode = !cm ? 0 : !strcmp(cm, "strict") ? 1 : !strcmp(cm, "off") ? 2 : 0;
   g_env = c;
@@ -264,6 +264,15 @@ struct annhip_workspace {
   }
 };
 
+// the one narrow row storage this library serves (RN, ann_device.h); the other library's value is refused
+#ifdef USE_FLOAT
+#define ANNHIP_ROWS_NARROW ANNHIP_ROWS_F16
+#define ANN_NARROW_WHAT "binary16"
+#else
+#define ANNHIP_ROWS_NARROW ANNHIP_ROWS_F32
+#define ANN_NARROW_WHAT "binary32"
+#endif
+
 struct annhip_index {
   size_t n = 0, k = 0, d = 0, ds = 0, lo = 0, hi = 0;
   int T = 0;
@@ -299,7 +308,7 @@ struct annhip_index {
   int gather_slots = 0;   // annhip_sh_stage1 as a persistent grid holding this many waves per SIMD (0 = one workgroup per query)
   int fixed = 0;          // annhip_index_set_fixed: opt-in non-parity query mode (Q1/Q2 undone)
   int rows = ANNHIP_ROWS_NATIVE;  // annhip_index_set_rows: which copy of the point rows the single-device query reads
-  RH *d_points_h = NULL;          // binary16 copy of the rows (made on the first ANNHIP_ROWS_F16, kept until destroy/reshard)
+  RN *d_points_h = NULL;          // narrow copy of the rows (made on the first ANNHIP_ROWS_NARROW, kept until destroy/reshard)
 };
 
 static QParams make_params(const annhip_index *ix) {
@@ -321,7 +330,7 @@ static QParams make_params(const annhip_index *ix) {
 // QParams of the single-device query path (annhip_query / _on / _slice, annhip_stream_*): the rows the index is set to
 static QParams query_params(const annhip_index *ix) {
   QParams P = make_params(ix);
-  if (ix->rows == ANNHIP_ROWS_F16) P.points_h = ix->d_points_h;
+  if (ix->rows == ANNHIP_ROWS_NARROW) P.points_h = ix->d_points_h;
   return P;
 }
 
@@ -416,34 +425,46 @@ __global__ void rows_to_half_kernel(size_t count, const float *__restrict__ in, 
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
     out[e] = __float2half_rn(in[e]);
 }
+static void rows_to_narrow(size_t count, const FT *in, RN *out) {
+  rows_to_half_kernel<<<grid_for(count, 256, 1u << 20), 256>>>(count, in, reinterpret_cast<__half *>(out));
+}
+#else
+// rows -> binary32, round to nearest even (overflow -> +-inf, subnormals kept, NaN stays NaN): one v_cvt_f32_f64 under the
+// kernel descriptor's default mode (both round modes 0 = nearest even, both denorm modes 3 = kept on input and output)
+__global__ void rows_to_float_kernel(size_t count, const double *__restrict__ in, float *__restrict__ out) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
+    out[e] = (float)in[e];
+}
+static void rows_to_narrow(size_t count, const FT *in, RN *out) {
+  rows_to_float_kernel<<<grid_for(count, 256, 1u << 20), 256>>>(count, in, out);
+}
 #endif
 
 extern "C" int annhip_index_set_rows(annhip_index *ix, int rows) {
-  if (rows != ANNHIP_ROWS_NATIVE && rows != ANNHIP_ROWS_F16) {
-    fprintf(stderr, "annhip_index_set_rows: unknown row storage %d (ANNHIP_ROWS_NATIVE = 0, ANNHIP_ROWS_F16 = 1)\n", rows);
+  if (rows != ANNHIP_ROWS_NATIVE && rows != ANNHIP_ROWS_F16 && rows != ANNHIP_ROWS_F32) {
+    fprintf(stderr, "annhip_index_set_rows: unknown row storage %d (ANNHIP_ROWS_NATIVE = 0, ANNHIP_ROWS_F16 = 1, "
+                    "ANNHIP_ROWS_F32 = 2)\n", rows);
     return -1;
   }
-#ifndef USE_FLOAT
-  if (rows == ANNHIP_ROWS_F16) {
-    fprintf(stderr, "annhip_index_set_rows: binary16 rows are a feature of the f32 library only\n");
+  if (rows != ANNHIP_ROWS_NATIVE && rows != ANNHIP_ROWS_NARROW) {
+    fprintf(stderr, "annhip_index_set_rows: %s rows are a feature of the %s library only\n",
+            rows == ANNHIP_ROWS_F16 ? "binary16" : "binary32", rows == ANNHIP_ROWS_F16 ? "f32" : "f64");
     return -1;
   }
-#else
-  if (rows == ANNHIP_ROWS_F16) {
+  if (rows == ANNHIP_ROWS_NARROW) {
     if (!(ix->lo == 0 && ix->hi == ix->n)) {
-      fprintf(stderr, "annhip_index_set_rows: binary16 rows need the whole index on this device (rows [0, n))\n");
+      fprintf(stderr, "annhip_index_set_rows: " ANN_NARROW_WHAT " rows need the whole index on this device (rows [0, n))\n");
       return -1;
     }
     if (!ix->d_points_h) {  // first enable: the copy is made on the device and kept (switching back and forth is free)
       const size_t count = ix->n * ix->d;
-      ix->d_points_h = dev_alloc<RH>(count);
+      ix->d_points_h = dev_alloc<RN>(count);
       HIPCHECK(hipDeviceSynchronize());  // the native rows may have been written on another stream
-      rows_to_half_kernel<<<grid_for(count, 256, 1u << 20), 256>>>(count, ix->d_points, reinterpret_cast<__half *>(ix->d_points_h));
+      rows_to_narrow(count, ix->d_points, ix->d_points_h);
       HIPCHECK(hipGetLastError());
       HIPCHECK(hipDeviceSynchronize());
     }
   }
-#endif
   ix->rows = rows;
   return 0;
 }
@@ -503,7 +524,7 @@ extern "C" annhip_index *annhip_index_create(const save_t *save, const ftype *po
 extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points_dev, size_t row_lo, size_t row_hi) {
   if (row_lo > row_hi || row_hi > ix->n) die("bad row range");
   HIPCHECK(hipDeviceSynchronize());
-  drop_half_rows(ix);  // binary16 rows are for the whole index on one device: a resharded index reads native rows
+  drop_half_rows(ix);  // narrow rows are for the whole index on one device: a resharded index reads native rows
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -656,17 +677,15 @@ static void with_value(Ints<Vs...>, int v, F &&f) {
   if (!((v == Vs && (f(Int<Vs>{}), true)) || ...)) die("no kernel instantiated for this layout code / template argument");
 }
 
-// The query kernels that read point rows come in two row types: f(TypeTag<RT>{}) with RT = RH (binary16) where
-// QParams::points_h is set -- f32 library only -- and FT otherwise.
+// The query kernels that read point rows come in two row types: f(TypeTag<RT>{}) with RT = RN (the library's narrow
+// type: binary16 in the f32 library, binary32 in the f64 library) where QParams::points_h is set, and FT otherwise.
 template <typename T>
 struct TypeTag {
   typedef T type;
 };
 template <typename F>
 static void with_rows(const QParams &P, F &&f) {
-#ifdef USE_FLOAT
-  if (P.points_h) return f(TypeTag<RH>{});
-#endif
+  if (P.points_h) return f(TypeTag<RN>{});
   f(TypeTag<FT>{});
 }
 
@@ -2569,19 +2588,18 @@ static void query_single_end(annhip_index *ix, size_t ycnt, size_t *result, ftyp
 }
 
 // ANN_HIP_ROWS before each query_gpu() step: the resident single-device index (ix; NULL = a sharded mode) is set to the
-// switch's row storage -- idempotent, so annhip_reload_env() takes effect on the next call.  Where binary16 rows do not
-// exist (f64 library, sharded modes) one warning per reading of the environment, and the rows stay native.
+// switch's row storage -- idempotent, so annhip_reload_env() takes effect on the next call.  Where the narrow rows asked
+// for do not exist (the other library's type, sharded modes) one warning per reading of the environment, and the rows
+// stay native.
 static void env_rows_apply(annhip_index *ix) {
   const int want = env().rows;
-  bool can = ix != NULL;
-#ifndef USE_FLOAT
-  can = false;
-#endif
-  if (want == ANNHIP_ROWS_F16 && !can) {
+  if (want != ANNHIP_ROWS_NATIVE && (want != ANNHIP_ROWS_NARROW || !ix)) {
     if (!g_env.rows_warned)
-      fprintf(stderr, "ANN_HIP_ROWS=f16: binary16 rows need the f32 library and one device (not ANN_HIP_DEVICES / "
-                      "ANN_HIP_VIRTUAL_SHARDS > 1); the rows stay native\n");
+      fprintf(stderr, "ANN_HIP_ROWS=%s: %s rows need the %s library and one device (not ANN_HIP_DEVICES / "
+                      "ANN_HIP_VIRTUAL_SHARDS > 1); the rows stay native\n", want == ANNHIP_ROWS_F16 ? "f16" : "f32",
+              want == ANNHIP_ROWS_F16 ? "binary16" : "binary32", want == ANNHIP_ROWS_F16 ? "f32" : "f64");
     g_env.rows_warned = true;
+    if (ix) annhip_index_set_rows(ix, ANNHIP_ROWS_NATIVE);  // "stay native" also after a switch this library did serve
     return;
   }
   if (ix && annhip_index_set_rows(ix, want) != 0) die("ANN_HIP_ROWS: annhip_index_set_rows failed");

@@ -55,8 +55,9 @@ struct QParams {
                      // (grid == qn: one query per workgroup; a smaller, PERSISTENT grid leaves wave slots to other streams)
   u32 fixed;         // opt-in non-parity mode (annhip_index_set_fixed): a query reads ITS OWN codes (Q2 undone); the host
                      // also sets P1 = Lc1 = L1 (every slot is a candidate, Q1 undone) and no network decides an order
-  const RH *points_h = nullptr;  // the rows rounded to binary16 (annhip_index_set_rows; f32 library, whole index), or NULL:
-                                 // the kernels instantiated with RT = RH read these instead (the host dispatches on it)
+  const RN *points_h = nullptr;  // the rows rounded to the library's narrow type (annhip_index_set_rows: binary16 in the f32
+                                 // library, binary32 in the f64 library; whole index), or NULL: the kernels instantiated
+                                 // with RT = RN read these instead (the host dispatches on it)
 };
 
 #define ANN_S1_CHUNK 1024  // slots whose valid ids one wave stages in LDS at a time
@@ -82,14 +83,14 @@ __device__ __forceinline__ VT load_row_chunk(const VT *p) {
   }
 }
 
-// The point rows the query kernels read: native (RT = FT) or binary16 (RT = RH, QParams::points_h).
+// The point rows the query kernels read: native (RT = FT) or narrow (RT = RN, QParams::points_h).
 template <typename RT>
 __device__ __forceinline__ const RT *q_rows(const QParams &P) {
   if constexpr (std::is_same<RT, FT>::value) return P.points;
   else return P.points_h;
 }
-// Chunk `ci` (ANN_VEC elements) of an aligned row, as loaded: a 16-byte VT of native rows, or 8 bytes of 4 halves --
-// the same element-to-lane map either way, hence the same tree.
+// Chunk `ci` (ANN_VEC elements) of an aligned row, as loaded: a 16-byte VT of native rows, or 8 bytes of 4 halves (f32 library) /
+// 2 floats (f64 library) -- the same element-to-lane map either way, hence the same tree.
 template <typename RT, bool NT>
 __device__ __forceinline__ typename RowRaw<RT>::T load_row_raw(const RT *row, int ci) {
   if constexpr (std::is_same<RT, FT>::value) {
@@ -103,7 +104,7 @@ __device__ __forceinline__ typename RowRaw<RT>::T load_row_raw(const RT *row, in
 }
 
 // Chunk `ci` of a row of d elements in the layouts D < 0.  Aligned layouts: one 16-byte load (NT as above; 8 bytes for a
-// row of halves); the unaligned one: element by element, zeros beyond d (never read by the tree, which starts at d).
+// narrow row); the unaligned one: element by element, zeros beyond d (never read by the tree, which starts at d).
 template <int D, bool NT, typename RT>
 __device__ __forceinline__ typename RowRaw<RT>::T oc_load_chunk(const RT *row, int ci, int d) {
   if constexpr (OcCode<D>::UA) {

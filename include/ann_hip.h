@@ -68,9 +68,20 @@ void annhip_index_set_fixed(annhip_index *ix, int fixed);
  * -1 with one line on stderr for ANNHIP_ROWS_F16 in the f64 library, ANNHIP_ROWS_F16 on an index whose rows are not
  * [0, n) (resharded), or an unknown value; ANNHIP_ROWS_NATIVE is accepted everywhere.  annhip_index_reshard returns the
  * index to native rows and frees the copy; the annhip_sh_* staged calls always read the native rows.
- * annhip_index_rows() = the current setting.  Drop-in path: ANN_HIP_ROWS=f16. */
+ * annhip_index_rows() = the current setting.  Drop-in path: ANN_HIP_ROWS=f16.
+ *
+ * ANNHIP_ROWS_F32 is the same mode for the f64 library, whose narrow row type is IEEE binary32: the results are exactly
+ * the reference's for query(save, f(P), y), f(P) = the double rows rounded to binary32 (round to nearest even; overflow
+ * -> +-inf, binary32 subnormals kept, NaN stays NaN) and widened back -- numpy's P.astype(np.float32).astype(np.float64).
+ * save is built from the double rows, the queries stay double, every distance is computed in double, in the reference's
+ * tree order, without FMA, from the exactly widened floats.  The copy takes n*d*4 bytes and a query moves half the row
+ * bytes (d = 256: 1024 instead of 2048 per candidate).  All the rules above hold alike: first enable converts, native
+ * rows stay, destroy and reshard free the copy, rows [0, n) on this device, annhip_sh_* / precomp / the recall scorer
+ * read native rows, fixed mode composes.  Each library serves its own narrow type only: -1 with one line on stderr for
+ * ANNHIP_ROWS_F32 in the f32 library, as for ANNHIP_ROWS_F16 in the f64 library.  Drop-in path: ANN_HIP_ROWS=f32. */
 #define ANNHIP_ROWS_NATIVE 0
 #define ANNHIP_ROWS_F16 1
+#define ANNHIP_ROWS_F32 2
 int annhip_index_set_rows(annhip_index *ix, int rows);
 int annhip_index_rows(const annhip_index *ix);
 /* Point-shard an index that was built from all n rows: from now on this device owns rows [row_lo,row_hi) only

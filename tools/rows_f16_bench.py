@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""tools/rows_f16_bench.py -- native vs binary16 point rows (annhip_index_set_rows) on ONE index and the same batches.
+"""tools/rows_f16_bench.py -- native vs narrow point rows (annhip_index_set_rows) on ONE index and the same batches:
+binary16 rows in the f32 library (the default), binary32 rows in the f64 library (--dtype f64).
 
-    python tools/rows_f16_bench.py [--points N] [--dim d] [--steps K] [--warmup W] [--rounds R] [--data randn|randnorm]
+    python tools/rows_f16_bench.py [--dtype f32|f64] [--points N] [--dim d] [--knn k] [--steps K] [--warmup W]
+                                   [--rounds R] [--data randn|randnorm]
 
-Workload: bench.py's cfg3 by default (N=10M, d=128, k=10, tries=10, Q=10k per step, float).  The index is built once
-(precomp from the float rows); the binary16 copy of the rows is made once (the first set_rows("f16")).  Then:
-  * timing: R rounds, each timing the K batches with native rows, then with binary16 rows -- the modes alternate in one
+Workload: bench.py's cfg3 by default (N=10M, d=128, k=10, tries=10, Q=10k per step, float); cfg5 is --dtype f64 --dim 256
+--knn 100.  The index is built once (precomp from the native rows); the narrow copy of the rows is made once (the first
+set_rows("f16") / set_rows("f32")).  Then:
+  * timing: R rounds, each timing the K batches with native rows, then with narrow rows -- the modes alternate in one
     process, so drift of clocks or temperature hits both;
   * stage 1: a separate pass per mode with the stage-1 HIP-event pair only (annhip_profile 2), and one with the row
     statistics (annhip_profile 1) for the algorithmic bytes;
-  * quality: recall against the FLOAT rows (annhip_recall_ranks, exact-rank brute force) on a sample of the first batch,
+  * quality: recall against the NATIVE rows (annhip_recall_ranks, exact-rank brute force) on a sample of the first batch,
     and the share of result ids that differ between the modes over one whole batch.
 Prints one JSON line.
 """
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--data", choices=["randn", "randnorm"], default="randn",
                     help="randn = torch.randn on the device (fast); randnorm = the reference drivers' stream (bench.py's default)")
     ap.add_argument("--recall-queries", type=int, default=512)
+    ap.add_argument("--dtype", choices=["f32", "f64"], default="f32",
+                    help="f32: float rows vs binary16 rows; f64: double rows (the reference's stock build) vs binary32 rows")
     args = ap.parse_args()
 
     import numpy as np
@@ -48,6 +53,8 @@ def main():
     from approximatenn_amd._lib import park_random
 
     n, d, k, T, Q = args.n, args.d, args.k, args.tries, args.q
+    prec = args.dtype
+    narrow, tdt, nsz = ("f16", torch.float32, 4) if prec == "f32" else ("f32", torch.float64, 8)  # nsz: native element bytes
     dev = torch.device("cuda", 0)
     libc = __import__("ctypes").CDLL("libc.so.6")
     with park_random():
@@ -56,7 +63,7 @@ def main():
     libc.srandom(args.seed)
     nb = args.warmup + args.steps
     if args.data == "randnorm":
-        host = A.synth_randnorm(n * d, "f32", reset=True).reshape(n, d)
+        host = A.synth_randnorm(n * d, prec, reset=True).reshape(n, d)
         with park_random():
             points = torch.from_numpy(host).to(dev)
         del host
@@ -64,28 +71,28 @@ def main():
         with park_random():
             gen = torch.Generator(device=dev)
             gen.manual_seed(args.seed)
-            points = torch.randn((n, d), device=dev, dtype=torch.float32, generator=gen)
+            points = torch.randn((n, d), device=dev, dtype=tdt, generator=gen)
     t0 = time.time()
     ix = A.Index.precomp(points, k, T)
     precomp_s = time.time() - t0
     with park_random():
         if args.data == "randnorm":
-            batches = [torch.from_numpy(A.synth_randnorm(Q * d, "f32").reshape(Q, d)).to(dev) for _ in range(nb)]
+            batches = [torch.from_numpy(A.synth_randnorm(Q * d, prec).reshape(Q, d)).to(dev) for _ in range(nb)]
         else:
-            batches = [torch.randn((Q, d), device=dev, dtype=torch.float32, generator=gen) for _ in range(nb)]
+            batches = [torch.randn((Q, d), device=dev, dtype=tdt, generator=gen) for _ in range(nb)]
         torch.cuda.synchronize()
     out_i = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    out_d = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_d = torch.empty((Q, k), dtype=tdt, device=dev)
 
     def run(ys):
         for y in ys:
             ix.query(y, out_ids=out_i, out_dists=out_d)
 
     t0 = time.time()
-    ix.set_rows("f16")  # the one conversion
+    ix.set_rows(narrow)  # the one conversion
     torch.cuda.synchronize()
     convert_s = time.time() - t0
-    modes = ("native", "f16")
+    modes = ("native", narrow)
     for m in modes:
         ix.set_rows(m)
         run(batches[:args.warmup])
@@ -117,8 +124,8 @@ def main():
         st1 = ix.stats(reset=True)
         ix.profile(0)
         rows_q = st1["s1_rows"] / max(st1["queries"], 1.0)
-        esz = 2 if m == "f16" else 4
-        bytes_q = rows_q * d * esz + ix.P1 * 4 + d * 4 + T * 4 + (k + 1) * 8   # bench.py's roofline_of, rows at esz
+        esz = nsz // 2 if m == narrow else nsz
+        bytes_q = rows_q * d * esz + ix.P1 * 4 + d * nsz + T * 4 + (k + 1) * (nsz + 4)   # bench.py's roofline_of, rows at esz
         ms = sorted(timed[m])[len(timed[m]) // 2]
         res[m] = {"ms_per_step": round(ms, 4), "ms_per_step_rounds": [round(v, 4) for v in timed[m]],
                   "qps": round(Q / (ms * 1e-3), 1), "stage1_ms": round(s1_ms, 4),
@@ -133,21 +140,22 @@ def main():
     qs = min(args.recall_queries, Q)
     ys = batches[0][:qs].contiguous()
     for m in modes:
-        rk = A.recall_ranks(points, ys, ids_of[m][:qs].contiguous())   # exact ranks against the FLOAT rows
+        rk = A.recall_ranks(points, ys, ids_of[m][:qs].contiguous())   # exact ranks against the NATIVE rows
         r = rk.to("cpu").double().numpy()
         res[m]["recall_at_k"] = round(float((r < k).mean()), 4)
         res[m]["recall_sample"] = {kk: round(v, 4) for kk, v in A.recall_summary(rk, k).items()}
-    diff = float((ids_of["native"] != ids_of["f16"]).double().mean().item())
+    diff = float((ids_of["native"] != ids_of[narrow]).double().mean().item())
     line = {
-        "workload": "N=%d d=%d k=%d tries=%d Q=%d float, %s data seed %d" % (n, d, k, T, Q, args.data, args.seed),
+        "workload": "N=%d d=%d k=%d tries=%d Q=%d %s, %s data seed %d" % (n, d, k, T, Q, "float" if prec == "f32" else "double",
+                                                                      args.data, args.seed),
         "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds,
-        "precomp_s": round(precomp_s, 2), "f16_conversion_s": round(convert_s, 3),
-        "native": res["native"], "f16": res["f16"],
-        "f16_over_native": {"ms_per_step": round(res["f16"]["ms_per_step"] / res["native"]["ms_per_step"], 4),
-                            "stage1_ms": round(res["f16"]["stage1_ms"] / res["native"]["stage1_ms"], 4)
-                            if res["native"]["stage1_ms"] > 0 else None},
+        "precomp_s": round(precomp_s, 2), narrow + "_conversion_s": round(convert_s, 3),
+        "native": res["native"], narrow: res[narrow],
+        narrow + "_over_native": {"ms_per_step": round(res[narrow]["ms_per_step"] / res["native"]["ms_per_step"], 4),
+                                  "stage1_ms": round(res[narrow]["stage1_ms"] / res["native"]["stage1_ms"], 4)
+                                  if res["native"]["stage1_ms"] > 0 else None},
         "ids_differing_share": round(diff, 5), "recall_queries": qs,
-        "index_bytes_rows": {"native": n * d * 4, "f16": n * d * 2},
+        "index_bytes_rows": {"native": n * d * nsz, narrow: n * d * nsz // 2},
     }
     ix.close()
     print(json.dumps(line))

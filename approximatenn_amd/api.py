@@ -228,6 +228,39 @@ def recall_ranks(points, y, guess, self_exclude=False):
     return ranks
 
 
+def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None):
+    """annhip_exact_knn: torch device tensors points [n,d], y [Q,d] -> (ids int64 [Q,k], sq dists [Q,k]): the exact k
+    nearest rows of every query, ordered by (distance, id), distances bit-identical to the query path's (include/ann_hip.h).
+    self_exclude: query q leaves out point q.  Precision from the dtype.  ValueError where the library refuses (k outside
+    1..1024 or larger than the rows on offer) and for tensors of mixed or unsupported dtype; the outputs are then untouched."""
+    import torch
+    if points.dtype != y.dtype or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("exact_knn: points and y must both be float32 or both float64")
+    if points.dim() != 2 or y.dim() != 2 or points.shape[1] != y.shape[1]:
+        raise ValueError("exact_knn: points [n,d] and y [Q,d] must have the same d")
+    assert points.is_cuda and y.is_cuda
+    lib = _lib.load("f32" if points.dtype == torch.float32 else "f64")
+    points, y, k = points.contiguous(), y.contiguous(), int(k)
+    Q = y.shape[0]
+    if k < 0:
+        raise ValueError("exact_knn: k must be in 1..1024")
+    ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=y.device)
+    dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=y.dtype, device=y.device)
+    assert ids.is_contiguous() and dists.is_contiguous() and ids.dtype == torch.int64 and dists.dtype == y.dtype
+    if lib.annhip_exact_knn(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(), int(bool(self_exclude)),
+                            ids.data_ptr(), dists.data_ptr()) != 0:
+        raise ValueError("annhip_exact_knn refused n=%d k=%d self_exclude=%r" % (points.shape[0], k, bool(self_exclude)))
+    return ids, dists
+
+
+def recall_at_k(guess, truth):
+    """Standard recall@k: the mean over queries of |guess[q] ∩ truth[q]| / k, for integer tensors guess [Q,kg] (as query()
+    returns them; ids >= n are its "no neighbour" marks and never match) and truth [Q,k] (exact_knn's ids)."""
+    k = truth.shape[1]
+    hit = (guess.unsqueeze(2) == truth.to(guess.device).unsqueeze(1)).any(dim=1)  # [Q,k]: truth id found among the guesses
+    return hit.double().sum(dim=1).div(k).mean().item()
+
+
 def checksum(t, prec="f32"):
     """annhip_checksum_dev: 64-bit content checksum of a contiguous torch device tensor."""
     assert t.is_cuda and t.is_contiguous()
@@ -351,6 +384,19 @@ class Index:
             nex = self.lib.annhip_query_on(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
                                            int(alias), mode, ids.data_ptr(), dists.data_ptr())
         return ids, dists, nex
+
+    def exact_query(self, y, alias=False):
+        """annhip_index_exact_query: the exact k nearest of the index's (native) rows for y [Q,d], k = the index's k ->
+        (ids int64 [Q,k], sq dists [Q,k]), ordered by (distance, id).  alias: query q leaves out point q.  ValueError where
+        the library refuses (a resharded index)."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        ids = torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
+        if self.lib.annhip_index_exact_query(self.h, Q, y.data_ptr(), int(bool(alias)), ids.data_ptr(), dists.data_ptr()) != 0:
+            raise ValueError("annhip_index_exact_query refused this index (resharded, or k larger than the rows on offer)")
+        return ids, dists
 
     def host_stream(self, max_ycnt, lanes=3):
         """annhip_stream_open: pipeline for host-resident (numpy) batches; see HostStream."""

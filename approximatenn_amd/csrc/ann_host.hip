@@ -24,6 +24,7 @@
 #include "ann_precomp_kernels.h"
 #include "ann_query_kernels.h"
 #include "ann_recall_kernels.h"
+#include "ann_exact_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -82,6 +83,7 @@ struct EnvCfg {
   int codes_lpq = 1;    // ANN_HIP_CODES_LPQ: 0 = the lanes-per-row hash kernel for every row length (A/B)
   int tie = 1;          // ANN_HIP_TIE: 0 = flagged rows always take the literal network (no tie path, ann_tie.h)
   int rows = 0;         // ANN_HIP_ROWS: f16 / f32 = query_gpu's resident single-device index reads narrow rows (annhip_index_set_rows)
+  int exact_ranges = 0;  // ANN_HIP_EXACT_RANGES: row ranges of annhip_exact_knn's scan (0 = from n, ycnt and the CU count; tests)
   bool rows_warned = false;  // ... and the one warning where it cannot (the other library's type, sharded modes) has been printed
 };
 static EnvCfg g_env;
@@ -115,6 +117,7 @@ static void load_env() {
   c.codes_lpq = env_int("ANN_HIP_CODES_LPQ", 1);
   c.s2_multi = env_int("ANN_HIP_S2_MULTI", 1);
   c.fin_tail = env_int("ANN_HIP_FIN_TAIL", 1);
+  c.exact_ranges = std::max(0, env_int("ANN_HIP_EXACT_RANGES", 0));
   const char *rw = getenv("ANN_HIP_ROWS");
   c.rows = !rw ? ANNHIP_ROWS_NATIVE : !strcmp(rw, "f16") ? ANNHIP_ROWS_F16 : !strcmp(rw, "f32") ? ANNHIP_ROWS_F32 : ANNHIP_ROWS_NATIVE;
   const char *cm = getenv("ANN_HIP_CACHE");
@@ -1775,6 +1778,143 @@ extern "C" void annhip_recall_ranks_host(size_t n, size_t d, size_t k, const fty
   if (dy != dp) HIPCHECK(hipFree(dy));
   HIPCHECK(hipFree(dg));
   HIPCHECK(hipFree(dr));
+}
+
+// ----------------------------------------------------------------------------- exact k nearest neighbours
+// Contract: include/ann_hip.h.  Kernels: ann_exact_kernels.h.  Synchronous, on the null stream like the recall scorer.
+#define ANN_EX_LDS_BUDGET (150 * 1024)       // one workgroup per CU
+#define ANN_EX_WS_BYTES ((size_t)256 << 20)  // workspace cap; larger batches go in chunks of queries
+#define ANN_EX_MIN_RANGE 1024                // rows per range at least: below that the merge outweighs the scan
+static int exact_refuse(const char *why) {
+  fprintf(stderr, "annhip_exact_knn: %s\n", why);
+  return 1;
+}
+static int exact_check(size_t n, size_t d, size_t k, int self) {
+  if (d < 1) return exact_refuse("d must be at least 1");
+  if (n >= 0xFFFFFFF0ull) return exact_refuse("n must fit 32 bits");
+  if (k < 1 || k > 1024) return exact_refuse("k must be in 1..1024");
+  if (k > n - (self && n ? 1 : 0) || !n) return exact_refuse("k exceeds the number of rows a query can be given");
+  return 0;
+}
+// Shape of one annhip_exact_knn call for a kernel that takes up to max_waves waves per workgroup; launch(grid, block,
+// smem, args) starts the scan of one chunk of queries.  prefetch: the kernel moves the next tile through registers.
+template <typename Launch>
+static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
+                     FT *dists_dev, bool generic, int max_waves, bool prefetch, Launch &&launch) {
+  // LDS of a workgroup: the row tile, then per wave the selection buffers (and the query + tree scratch of the any-d path)
+  const size_t row_bytes = d * sizeof(FT);
+  const size_t cap = k + ANN_EX_SLACK;
+  size_t np = ANN_EX_GEN_ELEMS / d;
+  np = np < 1 ? 1 : (np > ANN_WAVE ? ANN_WAVE : np);
+  const size_t wave_bytes = sizeof(Key) * (ANN_EX_QB * cap + k) + (generic ? (((1 + np) * row_bytes + 15) & ~(size_t)15) : 0);
+  // tile: what the threads can keep in flight (ANN_EX_PF pieces of 16 bytes each) where the kernel prefetches
+  auto tile_rows_of = [&](size_t W, bool pf) {
+    return std::max<size_t>(1, (pf ? (size_t)ANN_EX_PF * 64 * W * 16 : (size_t)ANN_EX_GEN_TILE_BYTES) / row_bytes);
+  };
+  auto smem_of = [&](size_t W, bool pf) { return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes; };
+  size_t W = (size_t)max_waves;
+  while (W > 1 && smem_of(W, prefetch) > ANN_EX_LDS_BUDGET) W--;
+  if (prefetch && row_bytes > (size_t)ANN_EX_PF * 64 * W * 16) prefetch = false;  // one row is more than the threads hold
+  const size_t smem = smem_of(W, prefetch);
+  if (smem > 160 * 1024) return exact_refuse("row too long for the LDS of one CU");
+  const size_t tile_rows = tile_rows_of(W, prefetch);
+  const size_t qpg = W * ANN_EX_QB;  // queries per workgroup
+  // Row ranges: enough workgroups for several rounds over the CUs at small ycnt, one range where the query groups fill
+  // the chip already; a range is long enough that its first rows (every one a survivor until k are known) do not count.
+  const size_t cus = (size_t)device_cus(), qgroups_all = (ycnt + qpg - 1) / qpg;
+  size_t ranges = (8 * cus + qgroups_all - 1) / qgroups_all;
+  ranges = std::min(ranges, std::max<size_t>(1, n / std::max<size_t>(ANN_EX_MIN_RANGE, 256 * k)));
+  if (ranges > 1) {  // the last round over the CUs should be full: of r/2..r ranges take the count that wastes least
+    size_t best = ranges;
+    double best_waste = 1e30;
+    for (size_t r = ranges; r >= std::max<size_t>(1, ranges / 2); r--) {
+      const double wgs = (double)(qgroups_all * r), rounds = ceil(wgs / (double)cus);
+      const double waste = rounds * (double)cus / wgs;
+      if (waste < best_waste - 1e-9) best_waste = waste, best = r;
+    }
+    ranges = best;
+  }
+  if (env().exact_ranges) ranges = (size_t)env().exact_ranges;
+  ranges = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ranges, n), std::max<size_t>(1, 16384 / k)));
+  const size_t range_rows = (n + ranges - 1) / ranges;
+  ranges = (n + range_rows - 1) / range_rows;  // no empty range
+  size_t qchunk = ANN_EX_WS_BYTES / (ranges * k * sizeof(Key));
+  qchunk = std::max(qpg, qchunk / qpg * qpg);
+  qchunk = std::min(qchunk, (ycnt + qpg - 1) / qpg * qpg);
+  Key *ws = dev_alloc<Key>(qchunk * ranges * k);
+  ExArgs A;
+  A.points = pts, A.y = y, A.ws = ws;
+  A.n = (u32)n, A.range_rows = (u32)range_rows, A.d = (int)d, A.k = (int)k, A.self = self ? 1 : 0;
+  A.tile_rows = (int)tile_rows, A.cap = (int)cap, A.ranges = (int)ranges, A.prefetch = prefetch ? 1 : 0;
+  for (size_t q0 = 0; q0 < ycnt; q0 += qchunk) {
+    const size_t qn = std::min(qchunk, ycnt - q0);
+    A.q0 = (u32)q0, A.qn = (u32)qn;
+    launch(dim3((unsigned)((qn + qpg - 1) / qpg), (unsigned)ranges), dim3((unsigned)(64 * W)), smem, A);
+    hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)((qn + 3) / 4)), dim3(256), 0, 0, ws, (u32)qn, (int)ranges, (int)k,
+                       ids_dev + q0 * k, dists_dev + q0 * k);
+    HIPCHECK(hipGetLastError());
+  }
+  HIPCHECK(hipStreamSynchronize(0));
+  HIPCHECK(hipFree(ws));
+  return 0;
+}
+
+extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                                int self, size_t *ids_dev, ftype *dists_dev) {
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  if (!ycnt) return 0;
+  gpu_init();
+  const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  const int code = layout_code(d);
+  if (layout_is_generic(code))
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_generic_kernel, smem);
+                       hipLaunchKernelGGL(exact_scan_generic_kernel, grid, block, smem, 0, A);
+                     });
+  int rc = 1;
+  with_value(QueryLayouts{}, code, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D != 0 && !OcCode<D>::GEN)
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_kernel<D>, smem);
+                       hipLaunchKernelGGL(exact_scan_kernel<D>, grid, block, smem, 0, A);
+                     });
+  });
+  return rc;
+}
+
+extern "C" int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
+                                     int self, size_t *ids, ftype *dists) {
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  if (!ycnt) return 0;
+  RandGuard keep_callers_stream;
+  gpu_init();
+  FT *dp = dev_alloc<FT>(n * d), *dy = (y == points) ? dp : dev_alloc<FT>(ycnt * d);
+  size_t *di = dev_alloc<size_t>(ycnt * k);
+  FT *dd = dev_alloc<FT>(ycnt * k);
+  HIPCHECK(hipMemcpy(dp, points, sizeof(FT) * n * d, hipMemcpyHostToDevice));
+  if (dy != dp) HIPCHECK(hipMemcpy(dy, y, sizeof(FT) * ycnt * d, hipMemcpyHostToDevice));
+  const int rc = annhip_exact_knn(n, d, k, reinterpret_cast<const ftype *>(dp), ycnt, reinterpret_cast<const ftype *>(dy), self, di,
+                                  reinterpret_cast<ftype *>(dd));
+  if (!rc) {
+    HIPCHECK(hipMemcpy(ids, di, sizeof(size_t) * ycnt * k, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(dists, dd, sizeof(FT) * ycnt * k, hipMemcpyDeviceToHost));
+  }
+  HIPCHECK(hipFree(dp));
+  if (dy != dp) HIPCHECK(hipFree(dy));
+  HIPCHECK(hipFree(di));
+  HIPCHECK(hipFree(dd));
+  return rc;
+}
+
+extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t *ids_dev,
+                                        ftype *dists_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  return annhip_exact_knn(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias, ids_dev,
+                          dists_dev);
 }
 
 // ----------------------------------------------------------------------------- precomp

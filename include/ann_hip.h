@@ -295,6 +295,29 @@ void annhip_recall_ranks(size_t n, size_t d, size_t k, const ftype *points_dev, 
 void annhip_recall_ranks_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
                               const size_t *guess, int self, unsigned long long *ranks_host);
 
+/* ---- exact k nearest neighbours (ground truth for recall@k) ------------------------------------------- */
+/* For every query q of y[0..ycnt), over the n rows of points: dist(q, i) is the squared L2 distance exactly as the query
+ * path computes it (df = y[q][z] - p[i][z], df * df, no contraction, summed by the reference's in-place halving tree with
+ * the odd element folded into z == 0): bit-identical to what query() returns for the same pair, for every d >= 1.
+ * ids[q][0..k) / dists[q][0..k) are the k smallest pairs under the total order (distance ascending, then id ascending),
+ * written in that order.  This tie rule is this function's own: the reference orders equal distances by the comparator
+ * sequence of its sort network over a candidate row, which has no meaning for a full scan.  +inf distances (overflow) are
+ * ordinary values and sort last, by id.  Rows or queries holding NaN: unspecified.
+ * self != 0: point q is left out for query q (the exact k-NN graph of the points themselves, as in annhip_recall_ranks).
+ * Refused on the host with a message on stderr and a non-zero return code, nothing launched, outputs untouched:
+ * k outside 1..1024, k > n - (self ? 1 : 0), n >= 0xFFFFFFF0.  ycnt == 0 returns 0 and does nothing.
+ * Device pointers; synchronous; 0 = done. */
+int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                     int self, size_t *ids_dev, ftype *dists_dev);
+/* The same with HOST pointers in and out, for plain-C drivers. */
+int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
+                          int self, size_t *ids, ftype *dists);
+/* The same over the rows an index already holds, with the index's own k; alias as in annhip_query (query q leaves out
+ * point q).  Always reads the NATIVE rows, whatever annhip_index_set_rows says.  An index that does not hold rows [0, n)
+ * (a resharded one) is refused with a non-zero return code. */
+int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
+                             size_t *ids_dev, ftype *dists_dev);
+
 /* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /
  * rand_norm produce (/root/reference/time_results.c:10-13, randNorm.c:9-21), incl. the pending second value of a pair

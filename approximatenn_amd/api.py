@@ -345,6 +345,34 @@ class Index:
         """annhip_index_set_fixed: opt-in non-parity query mode (own hash codes, every candidate slot; include/ann_hip.h)."""
         self.lib.annhip_index_set_fixed(self.h, int(bool(on)))
 
+    def set_probe(self, pair_bits):
+        """annhip_index_set_probe: the recall knob of fixed mode -- per try, also probe the buckets reached by flipping two of
+        the query's `pair_bits` least certain hash bits (0 = plain fixed mode, the default; "all" = d_short, the whole
+        Hamming-2 ball; include/ann_hip.h).  No effect while fixed mode is off.  ValueError where the library refuses
+        (outside 0..d_short); the setting is then unchanged."""
+        code = -1 if pair_bits == "all" else pair_bits
+        if isinstance(code, bool) or not isinstance(code, int) or self.lib.annhip_index_set_probe(self.h, code) != 0:
+            raise ValueError("annhip_index_set_probe refused pair_bits=%r (d_short = %d)" % (pair_bits, self.d_short))
+
+    @property
+    def probe(self):
+        """annhip_index_probe: the current pair bits (an int; "all" reads back as d_short)."""
+        return int(self.lib.annhip_index_probe(self.h))
+
+    def probe_bits(self, y):
+        """annhip_probe_bits: what a fixed-mode query of y [Q,d] would probe with -> (codes int64 [Q,T] (code[q*T+t]),
+        bits uint8 [Q,T,b]: per (query, try) the b projection indices of smallest magnitude, ascending).  ValueError
+        while the probe setting is 0."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q, b = y.shape[0], self.probe
+        codes = torch.empty((Q, self.tries), dtype=torch.int32, device=y.device)
+        bits = torch.empty((Q, self.tries, b), dtype=torch.uint8, device=y.device)
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        if self.lib.annhip_probe_bits(self.h, stream, Q, y.data_ptr(), codes.data_ptr(), bits.data_ptr()) != 0:
+            raise ValueError("annhip_probe_bits: the probe setting is 0 (Index.set_probe)")
+        return codes.to(torch.int64) & 0xFFFFFFFF, bits
+
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
     # the names an index of each precision knows: every library serves its own narrow row type (ANNHIP_ROWS_F32 = 2)
     ROWS_BY_PREC = {"f32": ROWS, "f64": {"native": 0, "f32": 2}}

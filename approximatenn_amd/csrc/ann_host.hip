@@ -23,6 +23,7 @@
 #include "ann_hostpool.h"
 #include "ann_precomp_kernels.h"
 #include "ann_query_kernels.h"
+#include "ann_probe_kernels.h"
 #include "ann_recall_kernels.h"
 #include "ann_exact_kernels.h"
 
@@ -258,9 +259,10 @@ struct EventPair {
 // several HIP streams give each stream its own (annhip_workspace_create).
 struct annhip_workspace {
   DevBuf codes, cand_d, cand_i, nvt, nvo, top_i, top_d, flist, xids, xd, r2i, r2d, out_i, out_d;
+  DevBuf pbits;  // fixed mode with pair bits: u8[Q][T][b] ranked projection indices of this batch (annhip_index_set_probe)
   u32 *d_fcount = NULL;
   void release() {
-    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d};
+    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits};
     for (DevBuf *b : bufs) b->release();
     if (d_fcount) HIPCHECK(hipFree(d_fcount));
     d_fcount = NULL;
@@ -310,6 +312,7 @@ struct annhip_index {
   int gather_pieces = 1;  // annhip_sh_stage1 in this many launches (annhip_index_set_gather_pieces)
   int gather_slots = 0;   // annhip_sh_stage1 as a persistent grid holding this many waves per SIMD (0 = one workgroup per query)
   int fixed = 0;          // annhip_index_set_fixed: opt-in non-parity query mode (Q1/Q2 undone)
+  int probe = 0;          // annhip_index_set_probe: pair bits b of fixed mode (0 = own bucket + Hamming distance 1 only)
   int rows = ANNHIP_ROWS_NATIVE;  // annhip_index_set_rows: which copy of the point rows the single-device query reads
   RN *d_points_h = NULL;          // narrow copy of the rows (made on the first ANNHIP_ROWS_NARROW, kept until destroy/reshard)
 };
@@ -421,6 +424,15 @@ extern "C" void annhip_index_set_gather_slots(annhip_index *ix, int waves_per_si
   ix->gather_slots = waves_per_simd < 0 ? 0 : waves_per_simd > 8 ? 8 : waves_per_simd;
 }
 extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) { ix->fixed = fixed ? 1 : 0; }
+extern "C" int annhip_index_set_probe(annhip_index *ix, int pair_bits) {
+  if (pair_bits < ANNHIP_PROBE_ALL || pair_bits > (int)ix->ds) {
+    fprintf(stderr, "annhip_index_set_probe: pair bits %d outside 0..d_short = %d (ANNHIP_PROBE_ALL = -1)\n", pair_bits, (int)ix->ds);
+    return -1;
+  }
+  ix->probe = pair_bits == ANNHIP_PROBE_ALL ? (int)ix->ds : pair_bits;
+  return 0;
+}
+extern "C" int annhip_index_probe(const annhip_index *ix) { return ix->probe; }
 
 #ifdef USE_FLOAT
 // rows -> binary16, round to nearest even (overflow -> +-inf, subnormals kept, NaN stays NaN)
@@ -857,6 +869,107 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   if (ix) ix->s1_launches += 1;
 }
 
+// ---- fixed mode with pair bits (annhip_index_set_probe; ann_probe_kernels.h)
+// The hash kernels with the ranking: launch_codes' three forms, every query hashed; pbits u8[Q][T][pb].
+static void launch_codes_probe(const QParams &P, size_t Q, const FT *y, u32 *codes, unsigned char *pbits, int pb, hipStream_t s,
+                               u32 *zero_me = NULL) {
+  const int wpb = ANN_PROBE_WPB;
+  const size_t items = Q * (size_t)P.T;
+  if (!items) return;
+  if (pb < 1 || pb > P.ds || P.ds > 31) die("launch_codes_probe: pair bits outside 1..d_short");
+  if (d_is_fast(P.d) && (size_t)P.d * sizeof(FT) <= 512 && env().codes_lpq) {  // a lane per query
+    const size_t smem = sizeof(FT) * ((size_t)P.ds + 1) * P.d + sizeof(u32) * ANN_WAVE * ANN_LPQ_WAVES +
+                        sizeof(UB) * (size_t)P.ds * ANN_WAVE;
+    const dim3 grid((unsigned)((Q + ANN_WAVE - 1) / ANN_WAVE), (unsigned)P.T);
+    with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D > 0 && D * sizeof(FT) <= 512) {
+        allow_lds(codes_probe_lpq_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_probe_lpq_kernel<D>, grid, dim3(64 * ANN_LPQ_WAVES), smem, s, P, (int)Q, y, codes, zero_me, pb, pbits);
+      }
+    });
+  } else if (d_is_fast(P.d)) {  // workgroup = (try, run of queries); the try's projection rows live in LDS
+    const size_t smem = sizeof(FT) * (size_t)P.ds * P.d;
+    const dim3 grid((unsigned)((Q + ANN_CODES_QPB - 1) / ANN_CODES_QPB), (unsigned)P.T);
+    with_value(Pow2Layouts{}, layout_code(P.d, false), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D > 0) {
+        allow_lds(codes_probe_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_probe_kernel<D>, grid, dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me, pb, pbits);
+      }
+    });
+  } else {
+    const unsigned grid = (unsigned)((items + wpb - 1) / wpb);
+    const size_t smem = d_needs_lds_row(P.d) ? sizeof(FT) * wpb * 2 * (size_t)P.d : 0;
+    with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      if constexpr (D <= 0) {
+        allow_lds(codes_probe_kernel<D>, smem);
+        hipLaunchKernelGGL(codes_probe_kernel<D>, dim3(grid), dim3(64 * wpb), smem, s, P, (int)Q, y, codes, zero_me, pb, pbits);
+      }
+    });
+  }
+  HIPCHECK(hipGetLastError());
+}
+
+static size_t stage1_probe_lds_bytes(const QParams &P, int W, int K1, int cap, int pb) {
+  size_t b = sizeof(Key) * (size_t)W * cap + 2 * sizeof(Key) * (size_t)W * K1 + sizeof(TryInfo) * (size_t)P.T +
+             sizeof(u32 *) * (size_t)W * ANN_WAVE + sizeof(u32) * (size_t)W * ANN_S1_CHUNK +
+             sizeof(u32) * (size_t)W * ANN_WAVE + sizeof(u32) * (size_t)P.T + sizeof(int) * (size_t)W + sizeof(u32) * 4 +
+             (size_t)P.T * pb;
+  b = (b + 15) & ~(size_t)15;
+  if (d_needs_lds_row(P.d)) b += sizeof(FT) * (size_t)P.d * (1 + W);
+  return b;
+}
+
+// Stage 1 of fixed mode over 1 + ds + pb (pb - 1) / 2 buckets per try.  Waves per query from the RUN count: a run holds
+// at most par_maxes[t] ids, and a wave should see about a list (ANN_S1_CHUNK) of them to amortise its selection and the
+// merge -- the rule stage1_waves applies to P1, which says nothing about the pair runs.
+static void launch_stage1_probe(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
+                                const unsigned char *pbits, int pb, FT *cand_d, u32 *cand_i, u32 *nvt, u32 *nvo, hipStream_t s) {
+  if (!Q) return;
+  const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
+  size_t slots = 0;
+  for (int t = 0; t < P.T; t++) slots += (size_t)rpt * ix->h_tries[t].pm;
+  int W = (int)std::min<size_t>(4, std::max<size_t>(1, slots / ANN_S1_CHUNK));
+  if (env().s1_waves) W = env().s1_waves;
+  const int K1 = P.k + 1, cap = stage1_cap(W, K1);
+  const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
+  EventPair ev;
+  const bool prof = ix->profile;
+  if (prof) {
+    if (ix->ev_free.empty()) {
+      HIPCHECK(hipEventCreate(&ev.a));
+      HIPCHECK(hipEventCreate(&ev.b));
+    } else {
+      ev = ix->ev_free.back();
+      ix->ev_free.pop_back();
+    }
+    HIPCHECK(hipEventRecord(ev.a, s));
+  }
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      auto launch = [&](auto sg) {
+        constexpr int D = decltype(dd)::value;
+        constexpr bool SG = decltype(sg)::value;
+        using RT = typename decltype(rt)::type;
+        allow_lds(stage1_probe_kernel<D, SG, RT>, smem);
+        hipLaunchKernelGGL((stage1_probe_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
+                           pb, rpt, K1, cap, cand_d, cand_i, nvt, nvo);
+      };
+      if (ix->use_seg) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
+  });
+  HIPCHECK(hipGetLastError());
+  if (prof) {
+    HIPCHECK(hipEventRecord(ev.b, s));
+    ix->ev_used.push_back(ev);
+    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
+  }
+  ix->s1_launches += 1;
+}
+
 // bucket-centric stage 1 of precomp: returns false when the shape does not fit (caller uses the per-point kernel)
 static bool launch_stage1_bucket(const QParams &P, const TryInfo &one, size_t nbuckets, FT *cand_d, u32 *cand_i, u32 *nvt,
                                  u32 *nvo, hipStream_t s, u32 brem = 0, u32 bmod = 1) {
@@ -1157,9 +1270,15 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
   seg_mark(ix, marks, s);
   const u32 *codes = codes_ext;
   bool fcount_zeroed = codes_ready == 2;
+  const bool probing = ix->fixed && ix->probe > 0;  // parity-mode queries ignore the probe setting
+  unsigned char *pbits = NULL;
   if (!codes_ext) {
     u32 *own = (u32 *)ws.codes.need(sizeof(u32) * Q * P.T);
-    if (!codes_ready) {
+    if (probing) {  // fixed mode with pair bits: the hash kernel that also ranks the projections
+      pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
+      launch_codes_probe(P, Q, y, own, pbits, ix->probe, s, ws.d_fcount);
+      fcount_zeroed = true;
+    } else if (!codes_ready) {
       launch_codes(P, codes_needed(ix, Q), y, own, s, ws.d_fcount);  // also resets the batch's flagged-query counter
       fcount_zeroed = codes_needed(ix, Q) > 0;
     }
@@ -1182,7 +1301,8 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
     nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
     u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-    launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
+    if (probing) launch_stage1_probe(ix, P, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
+    else launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
     seg_mark(ix, marks, s);
     hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, P.k, K1, P.L1, P.P1,
                        cand_d, cand_i, nvt, top_i, top_d, k, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
@@ -1303,6 +1423,15 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
 extern "C" long annhip_query(annhip_index *ix, size_t Q, const ftype *y_dev, int alias, int mode, size_t *ids_dev,
                              ftype *dists_dev) {
   return query_impl(ix, ix->ws, ix->stream, Q, y_dev, alias, mode, ids_dev, dists_dev);
+}
+
+extern "C" int annhip_probe_bits(annhip_index *ix, void *hip_stream, size_t Q, const ftype *y_dev, uint32_t *codes_dev,
+                                 uint8_t *pbits_dev) {
+  if (ix->probe <= 0) return -1;
+  if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
+  launch_codes_probe(query_params(ix), Q, reinterpret_cast<const FT *>(y_dev), codes_dev, pbits_dev, ix->probe,
+                     (hipStream_t)hip_stream);
+  return 0;
 }
 
 extern "C" annhip_workspace *annhip_workspace_create(annhip_index *ix) {

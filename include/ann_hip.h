@@ -53,6 +53,29 @@ void annhip_index_set_gather_slots(annhip_index *ix, int waves_per_simd);
  * candidates, stage 2 likewise; (n, +inf) where fewer than k exist.  Not comparable with the reference -- checked
  * against a brute force over the same candidate sets (tests/test_gpu_fixed_mode.py).  precomp is unaffected. */
 void annhip_index_set_fixed(annhip_index *ix, int fixed);
+/* Query-directed multi-probe: the recall knob of fixed mode (default 0 = fixed mode as described above, bit for bit).
+ * For query x and try t let p[s], s = 0 .. d_short-1, be the projections the hash kernel computes (centred query .
+ * bases[t][s] in the reference's tree order: the value whose sign bit is bit d_short-1-s of the code).  Order the s by
+ * the key (|p[s]| as raw bits with the sign cleared, then s ascending): o[0], o[1], ...  With pair bits b
+ * (0 <= b <= d_short) the buckets probed for (x, t) are code ^ m for m in
+ *     {0}  u  {1 << z : 0 <= z < d_short}  u  {bit(o[u]) | bit(o[v]) : 0 <= u < v < b},   bit(s) = 1 << (d_short-1-s)
+ * i.e. 1 + d_short + b(b-1)/2 buckets: the two-bit flips among the b LEAST CERTAIN hash bits; b <= 1 adds nothing.
+ * Stage 1 returns the k smallest distinct (distance, id) keys among the valid ids of those buckets over all tries (self
+ * excluded when aliased), exactly as fixed mode defines its result; stage 2 is fixed mode's, unchanged.  +-0 projections
+ * have magnitude 0 and sort first; the order of NaN projections is unspecified.  The setting has an effect only while
+ * fixed mode is on: parity-mode queries ignore it and stay bit-identical to the reference.  Composes with
+ * annhip_index_set_rows, annhip_query_on (the ranked bits live in the batch's workspace) and annhip_stream_*.
+ * annhip_index_set_probe: 0 on success; -1 with one line on stderr and the setting unchanged for pair_bits < -1 or
+ * > d_short; ANNHIP_PROBE_ALL (-1) means d_short, the whole Hamming-2 ball.  annhip_index_probe: the current value (the
+ * resolved one, never -1).
+ * annhip_probe_bits runs the ranking hash kernel alone on hip_stream and returns what a query of this batch would use:
+ * codes_dev u32[ycnt][tries] (code[q*T+t], the same bits as the plain hash kernels write) and pbits_dev
+ * u8[ycnt][tries][b] = o[0..b); -1 (nothing launched) while the setting is 0. */
+enum { ANNHIP_PROBE_ALL = -1 };
+int annhip_index_set_probe(annhip_index *ix, int pair_bits);
+int annhip_index_probe(const annhip_index *ix);
+int annhip_probe_bits(annhip_index *ix, void *hip_stream, size_t ycnt, const ftype *y_dev, uint32_t *codes_dev,
+                      uint8_t *pbits_dev);
 /* Opt-in binary16 point rows (default ANNHIP_ROWS_NATIVE = the reference's results, bit for bit).  With ANNHIP_ROWS_F16,
  * annhip_query / annhip_query_on / annhip_query_slice / annhip_stream_* on this index return exactly what the reference
  * returns for query(save, h(P), y), where h(P) is the point matrix rounded to IEEE binary16 (round to nearest even;

@@ -228,11 +228,34 @@ def recall_ranks(points, y, guess, self_exclude=False):
     return ranks
 
 
-def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None):
+def pack_allow(allow):
+    """A numpy bool (or 0/1) array [n] -> the allow-list words uint32[ceil(n/32)] of annhip_index_set_filter: row i is bit
+    i & 31 of word i >> 5; the tail bits of the last word are zero."""
+    flags = np.ascontiguousarray(np.asarray(allow).reshape(-1) != 0)
+    by = np.packbits(flags, bitorder="little")
+    by = np.concatenate([by, np.zeros(-len(by) % 4, dtype=np.uint8)])
+    return by.view("<u4").astype(np.uint32)
+
+
+def _pack_allow_dev(lib, allow, n):
+    """A torch bool / uint8 device tensor [n] -> int32 device tensor holding the allow-list words (annhip_filter_pack)."""
+    import torch
+    if not isinstance(allow, torch.Tensor) or not allow.is_cuda or allow.dtype not in (torch.bool, torch.uint8) or allow.dim() != 1 or allow.shape[0] != n:
+        raise ValueError("allow must be a bool or uint8 device tensor of length n = %d" % n)
+    flags = allow.contiguous()
+    bits = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=allow.device)
+    lib.annhip_filter_pack(n, flags.data_ptr(), bits.data_ptr(), torch.cuda.current_stream(allow.device).cuda_stream)
+    torch.cuda.current_stream(allow.device).synchronize()  # the consumers run on the null stream / copy synchronously
+    return bits
+
+
+def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, allow=None):
     """annhip_exact_knn: torch device tensors points [n,d], y [Q,d] -> (ids int64 [Q,k], sq dists [Q,k]): the exact k
     nearest rows of every query, ordered by (distance, id), distances bit-identical to the query path's (include/ann_hip.h).
     self_exclude: query q leaves out point q.  Precision from the dtype.  ValueError where the library refuses (k outside
-    1..1024 or larger than the rows on offer) and for tensors of mixed or unsupported dtype; the outputs are then untouched."""
+    1..1024 or larger than the rows on offer) and for tensors of mixed or unsupported dtype; the outputs are then untouched.
+    allow: a bool device tensor [n] -- annhip_exact_knn_filtered: only rows with allow[i] set compete; a query with fewer
+    than k of them gets (n, +inf) in the tail."""
     import torch
     if points.dtype != y.dtype or points.dtype not in (torch.float32, torch.float64):
         raise ValueError("exact_knn: points and y must both be float32 or both float64")
@@ -247,6 +270,13 @@ def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None):
     ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=y.device)
     dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=y.dtype, device=y.device)
     assert ids.is_contiguous() and dists.is_contiguous() and ids.dtype == torch.int64 and dists.dtype == y.dtype
+    if allow is not None:
+        bits = _pack_allow_dev(lib, allow, points.shape[0])
+        rc = lib.annhip_exact_knn_filtered(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(),
+                                           int(bool(self_exclude)), bits.data_ptr(), ids.data_ptr(), dists.data_ptr())
+        if rc != 0:
+            raise ValueError("annhip_exact_knn_filtered refused n=%d k=%d self_exclude=%r" % (points.shape[0], k, bool(self_exclude)))
+        return ids, dists
     if lib.annhip_exact_knn(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(), int(bool(self_exclude)),
                             ids.data_ptr(), dists.data_ptr()) != 0:
         raise ValueError("annhip_exact_knn refused n=%d k=%d self_exclude=%r" % (points.shape[0], k, bool(self_exclude)))
@@ -372,6 +402,31 @@ class Index:
         if self.lib.annhip_probe_bits(self.h, stream, Q, y.data_ptr(), codes.data_ptr(), bits.data_ptr()) != 0:
             raise ValueError("annhip_probe_bits: the probe setting is 0 (Index.set_probe)")
         return codes.to(torch.int64) & 0xFFFFFFFF, bits
+
+    def set_filter(self, allow):
+        """annhip_index_set_filter: restrict fixed-mode queries (and exact_query) to the rows with allow[i] set.  allow:
+        None (clear), a torch bool or uint8 device tensor [n], or a numpy bool array [n]; the index keeps its own packed
+        copy.  ValueError for a wrong length and where the library refuses (fixed mode off, resharded index); the setting
+        is then unchanged.  set_fixed(False) and reshard drop the filter.  Do not change it while batches are in flight."""
+        if allow is None:
+            self.lib.annhip_index_set_filter(self.h, None, 0)
+            return
+        if isinstance(allow, np.ndarray):
+            if allow.shape != (self.n,):
+                raise ValueError("allow must have length n = %d" % self.n)
+            bits = pack_allow(allow)
+            rc = self.lib.annhip_index_set_filter(self.h, bits.ctypes.data, 0)
+        else:
+            bits = _pack_allow_dev(self.lib, allow, self.n)
+            rc = self.lib.annhip_index_set_filter(self.h, bits.data_ptr(), 1)
+        if rc != 0:
+            raise ValueError("annhip_index_set_filter refused (fixed mode off, or a resharded index)")
+
+    @property
+    def filter_count(self):
+        """annhip_index_filter_count: the number of allowed rows, or None while no filter is set."""
+        c = int(self.lib.annhip_index_filter_count(self.h))
+        return None if c < 0 else c
 
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
     # the names an index of each precision knows: every library serves its own narrow row type (ANNHIP_ROWS_F32 = 2)

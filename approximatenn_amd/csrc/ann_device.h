@@ -132,7 +132,10 @@ __device__ __forceinline__ FT key_dist(Key k) { return ft_from_bits(k.d); }
 __device__ __forceinline__ u32 key_id(Key k) { return (u32)k.i; }
 __device__ __forceinline__ bool key_less(Key a, Key b) { return a.d < b.d || (a.d == b.d && a.i < b.i); }
 __device__ __forceinline__ bool key_eq(Key a, Key b) { return a.d == b.d && a.i == b.i; }
-__device__ __forceinline__ Key key_max() { return Key{~0ull, ~0ull}; }
+// (the id half is 32 bits wide everywhere a key travels between lanes -- key_shfl_xor moves (u32)i -- so the largest key
+// has to survive that trip unchanged: with i = ~0ull wave_min_key() returned {~0, 0xFFFFFFFF} != key_max(), and
+// wave_select_smallest() then "found" (NaN, 0xFFFFFFFF) keys where fewer than `want` existed)
+__device__ __forceinline__ Key key_max() { return Key{~0ull, 0xFFFFFFFFull}; }
 __device__ __forceinline__ Key key_shfl_xor(Key k, int m) {
   Key o;
   o.d = ((u64)__shfl_xor((u32)(k.d >> 32), m) << 32) | __shfl_xor((u32)k.d, m);

@@ -26,6 +26,7 @@
 #include "ann_probe_kernels.h"
 #include "ann_recall_kernels.h"
 #include "ann_exact_kernels.h"
+#include "ann_filter_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -315,6 +316,8 @@ struct annhip_index {
   int probe = 0;          // annhip_index_set_probe: pair bits b of fixed mode (0 = own bucket + Hamming distance 1 only)
   int rows = ANNHIP_ROWS_NATIVE;  // annhip_index_set_rows: which copy of the point rows the single-device query reads
   RN *d_points_h = NULL;          // narrow copy of the rows (made on the first ANNHIP_ROWS_NARROW, kept until destroy/reshard)
+  u32 *filter = NULL;             // annhip_index_set_filter: the index's copy of the allow list, u32[ceil(n / 32)] (NULL = none)
+  long long filter_count = -1;    // allowed rows among [0, n), taken when the filter was set (-1 = no filter)
 };
 
 static QParams make_params(const annhip_index *ix) {
@@ -423,7 +426,54 @@ extern "C" void annhip_index_set_gather_pieces(annhip_index *ix, int pieces) { i
 extern "C" void annhip_index_set_gather_slots(annhip_index *ix, int waves_per_simd) {
   ix->gather_slots = waves_per_simd < 0 ? 0 : waves_per_simd > 8 ? 8 : waves_per_simd;
 }
-extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) { ix->fixed = fixed ? 1 : 0; }
+static void drop_filter(annhip_index *ix) {
+  if (ix->filter) HIPCHECK(hipFree(ix->filter));
+  ix->filter = NULL;
+  ix->filter_count = -1;
+}
+extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) {
+  ix->fixed = fixed ? 1 : 0;
+  if (!ix->fixed && ix->filter) {  // a parity-mode query has no notion of a filter: it must not look as if one applied
+    HIPCHECK(hipDeviceSynchronize());
+    drop_filter(ix);
+  }
+}
+// Contract: include/ann_hip.h.  Kernels: ann_filter_kernels.h.
+extern "C" int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, int bits_on_device) {
+  if (!bits) {
+    if (ix->filter) HIPCHECK(hipDeviceSynchronize());
+    drop_filter(ix);
+    return 0;
+  }
+  if (!ix->fixed) {
+    fprintf(stderr, "annhip_index_set_filter: fixed mode is off (annhip_index_set_fixed); parity-mode queries take no filter\n");
+    return -1;
+  }
+  if (ix->lo != 0 || ix->hi != ix->n) {
+    fprintf(stderr, "annhip_index_set_filter: the index does not hold rows [0, n) on this device (resharded)\n");
+    return -1;
+  }
+  const size_t nw = (ix->n + 31) / 32;
+  HIPCHECK(hipDeviceSynchronize());
+  if (!ix->filter) ix->filter = dev_alloc<u32>(nw);
+  HIPCHECK(hipMemcpy(ix->filter, bits, sizeof(u32) * nw, bits_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  unsigned long long *cnt = dev_alloc<unsigned long long>(1), host = 0;
+  HIPCHECK(hipMemset(cnt, 0, sizeof host));
+  filter_count_kernel<<<grid_for(nw, 256, 1024), 256>>>(ix->n, ix->filter, cnt);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(&host, cnt, sizeof host, hipMemcpyDeviceToHost));
+  HIPCHECK(hipFree(cnt));
+  ix->filter_count = (long long)host;
+  return 0;
+}
+extern "C" long long annhip_index_filter_count(const annhip_index *ix) { return ix->filter ? ix->filter_count : -1; }
+extern "C" int annhip_filter_pack(size_t n, const uint8_t *flags_dev, uint32_t *bits_dev, void *hip_stream) {
+  if (!n) return 0;
+  gpu_init();
+  filter_pack_kernel<<<grid_for((n + 63) / 64, 4, 4096), 256, 0, (hipStream_t)hip_stream>>>(n, flags_dev, bits_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
 extern "C" int annhip_index_set_probe(annhip_index *ix, int pair_bits) {
   if (pair_bits < ANNHIP_PROBE_ALL || pair_bits > (int)ix->ds) {
     fprintf(stderr, "annhip_index_set_probe: pair bits %d outside 0..d_short = %d (ANNHIP_PROBE_ALL = -1)\n", pair_bits, (int)ix->ds);
@@ -540,6 +590,7 @@ extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points
   if (row_lo > row_hi || row_hi > ix->n) die("bad row range");
   HIPCHECK(hipDeviceSynchronize());
   drop_half_rows(ix);  // narrow rows are for the whole index on one device: a resharded index reads native rows
+  drop_filter(ix);     // ... and so is the allow list
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -553,6 +604,7 @@ extern "C" void annhip_index_destroy(annhip_index *ix) {
   HIPCHECK(hipDeviceSynchronize());
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   drop_half_rows(ix);
+  drop_filter(ix);
   for (u32 *t : ix->d_tabs)
     if (t) HIPCHECK(hipFree(t));
   for (uint2 *sg : ix->d_segs)
@@ -970,6 +1022,54 @@ static void launch_stage1_probe(annhip_index *ix, const QParams &P, size_t Q, co
   ix->s1_launches += 1;
 }
 
+// Stage 1 of fixed mode with an allow list (annhip_index_set_filter; ann_filter_kernels.h): launch_stage1_probe's shape
+// for every pair-bit setting, pb = 0 included (1 + ds runs per try, no ranked bits).
+static void launch_stage1_filter(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
+                                 const unsigned char *pbits, int pb, const u32 *bits, FT *cand_d, u32 *cand_i, u32 *nvt,
+                                 u32 *nvo, hipStream_t s) {
+  if (!Q) return;
+  const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
+  size_t slots = 0;
+  for (int t = 0; t < P.T; t++) slots += (size_t)rpt * ix->h_tries[t].pm;
+  int W = (int)std::min<size_t>(4, std::max<size_t>(1, slots / ANN_S1_CHUNK));
+  if (env().s1_waves) W = env().s1_waves;
+  const int K1 = P.k + 1, cap = stage1_cap(W, K1);
+  const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
+  EventPair ev;
+  const bool prof = ix->profile;
+  if (prof) {
+    if (ix->ev_free.empty()) {
+      HIPCHECK(hipEventCreate(&ev.a));
+      HIPCHECK(hipEventCreate(&ev.b));
+    } else {
+      ev = ix->ev_free.back();
+      ix->ev_free.pop_back();
+    }
+    HIPCHECK(hipEventRecord(ev.a, s));
+  }
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      auto launch = [&](auto sg) {
+        constexpr int D = decltype(dd)::value;
+        constexpr bool SG = decltype(sg)::value;
+        using RT = typename decltype(rt)::type;
+        allow_lds(stage1_filter_kernel<D, SG, RT>, smem);
+        hipLaunchKernelGGL((stage1_filter_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
+                           pb, rpt, bits, K1, cap, cand_d, cand_i, nvt, nvo);
+      };
+      if (ix->use_seg) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
+  });
+  HIPCHECK(hipGetLastError());
+  if (prof) {
+    HIPCHECK(hipEventRecord(ev.b, s));
+    ix->ev_used.push_back(ev);
+    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
+  }
+  ix->s1_launches += 1;
+}
+
 // bucket-centric stage 1 of precomp: returns false when the shape does not fit (caller uses the per-point kernel)
 static bool launch_stage1_bucket(const QParams &P, const TryInfo &one, size_t nbuckets, FT *cand_d, u32 *cand_i, u32 *nvt,
                                  u32 *nvo, hipStream_t s, u32 brem = 0, u32 bmod = 1) {
@@ -1119,8 +1219,10 @@ static void launch_stage2_fused(const QParams &P, size_t Q, const FT *y, int ali
 static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y, int alias, u32 xbase, size_t nq,
                                         const u32 *top_i, const FT *top_d, u32 *out32, size_t *out64, FT *out_d,
                                         DevBuf &flist, u32 *d_fcount, DevBuf &r2i, DevBuf &r2d,
-                                        unsigned long long *exact_total, unsigned long long *rows_ctr, hipStream_t s) {
+                                        unsigned long long *exact_total, unsigned long long *rows_ctr, hipStream_t s,
+                                        const u32 *filter = NULL) {  // filter: fixed mode's allow list (stage2_filter_kernel)
   if (!nq) return true;
+  if (filter && !P.fixed) die("stage2_select_with_fallback: an allow list needs fixed mode");
   const int K1 = P.k + 1, W = 4, cap = stage1_cap(W, K1);
   const u32 P2 = (P.L2 < 16 || P.fixed) ? P.L2 : (u32)1 << ann_lg(P.L2);
   size_t smem = sizeof(Key) * (size_t)W * cap + 2 * sizeof(Key) * (size_t)W * K1 + sizeof(Key) * (size_t)P.k +
@@ -1138,6 +1240,12 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
         constexpr int D = decltype(dd)::value;
         using RT = typename decltype(rt)::type;
         using TT = std::remove_pointer_t<decltype(out)>;
+        if (filter) {
+          allow_lds((stage2_filter_kernel<D, TT, RT>), smem);
+          hipLaunchKernelGGL((stage2_filter_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
+                             top_i, top_d, filter, P2, K1, cap, out, out_d, fl, d_fcount, exact_total, rows_ctr, xbase);
+          return;
+        }
         allow_lds((stage2_select_kernel<D, TT, RT>), smem);
         hipLaunchKernelGGL((stage2_select_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
                            top_i, top_d, P2, K1, cap, out, out_d, fl, d_fcount, exact_total, rows_ctr, xbase);
@@ -1301,7 +1409,9 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
     nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
     u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-    if (probing) launch_stage1_probe(ix, P, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
+    if (ix->filter)  // allow list: one kernel family for every pair-bit setting (b = 0: no ranked bits)
+      launch_stage1_filter(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s);
+    else if (probing) launch_stage1_probe(ix, P, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
     else launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
     seg_mark(ix, marks, s);
     hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, P.k, K1, P.L1, P.P1,
@@ -1310,7 +1420,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     seg_mark(ix, marks, s);
     FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * k);
     if (!stage2_select_with_fallback(P, Q, y, alias, 0, Q, top_i, top_d, NULL, ids_dev, out_d, ws.flist, ws.d_fcount, ws.r2i,
-                                     ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s))
+                                     ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter))
       die("fixed mode: stage-2 shape not supported");
     seg_mark(ix, marks, s);
     seg_mark(ix, marks, s);
@@ -1929,7 +2039,7 @@ static int exact_check(size_t n, size_t d, size_t k, int self) {
 // smem, args) starts the scan of one chunk of queries.  prefetch: the kernel moves the next tile through registers.
 template <typename Launch>
 static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
-                     FT *dists_dev, bool generic, int max_waves, bool prefetch, Launch &&launch) {
+                     FT *dists_dev, bool generic, int max_waves, bool prefetch, bool filtered, Launch &&launch) {
   // LDS of a workgroup: the row tile, then per wave the selection buffers (and the query + tree scratch of the any-d path)
   const size_t row_bytes = d * sizeof(FT);
   const size_t cap = k + ANN_EX_SLACK;
@@ -1940,7 +2050,10 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
   auto tile_rows_of = [&](size_t W, bool pf) {
     return std::max<size_t>(1, (pf ? (size_t)ANN_EX_PF * 64 * W * 16 : (size_t)ANN_EX_GEN_TILE_BYTES) / row_bytes);
   };
-  auto smem_of = [&](size_t W, bool pf) { return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes; };
+  auto smem_of = [&](size_t W, bool pf) {  // (filtered: the tile's words of the allow list behind the waves' buffers)
+    return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +
+           (filtered ? sizeof(u32) * ANN_EX_TBITS(tile_rows_of(W, pf)) : 0);
+  };
   size_t W = (size_t)max_waves;
   while (W > 1 && smem_of(W, prefetch) > ANN_EX_LDS_BUDGET) W--;
   if (prefetch && row_bytes > (size_t)ANN_EX_PF * 64 * W * 16) prefetch = false;  // one row is more than the threads hold
@@ -1981,11 +2094,43 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
     launch(dim3((unsigned)((qn + qpg - 1) / qpg), (unsigned)ranges), dim3((unsigned)(64 * W)), smem, A);
     hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)((qn + 3) / 4)), dim3(256), 0, 0, ws, (u32)qn, (int)ranges, (int)k,
                        ids_dev + q0 * k, dists_dev + q0 * k);
+    if (filtered)  // fewer than k allowed rows: the "no row" padding becomes (n, +inf)
+      exact_tail_kernel<<<grid_for(qn * k, 256, 1024), 256>>>(qn * k, n, ids_dev + q0 * k, dists_dev + q0 * k);
     HIPCHECK(hipGetLastError());
   }
   HIPCHECK(hipStreamSynchronize(0));
   HIPCHECK(hipFree(ws));
   return 0;
+}
+
+extern "C" int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt,
+                                         const ftype *y_dev, int self, const uint32_t *bits_dev, size_t *ids_dev,
+                                         ftype *dists_dev) {
+  if (!bits_dev) return annhip_exact_knn(n, d, k, points_dev, ycnt, y_dev, self, ids_dev, dists_dev);
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  if (!ycnt) return 0;
+  gpu_init();
+  const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  const u32 *bits = bits_dev;
+  const int code = layout_code(d);
+  if (layout_is_generic(code))
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, true,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_generic_filtered_kernel, smem);
+                       hipLaunchKernelGGL(exact_scan_generic_filtered_kernel, grid, block, smem, 0, A, bits);
+                     });
+  int rc = 1;
+  with_value(QueryLayouts{}, code, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D != 0 && !OcCode<D>::GEN)
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, true,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_filtered_kernel<D>, smem);
+                       hipLaunchKernelGGL(exact_scan_filtered_kernel<D>, grid, block, smem, 0, A, bits);
+                     });
+  });
+  return rc;
 }
 
 extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
@@ -1997,7 +2142,7 @@ extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *point
   FT *dd = reinterpret_cast<FT *>(dists_dev);
   const int code = layout_code(d);
   if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false,
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, false,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_generic_kernel, smem);
                        hipLaunchKernelGGL(exact_scan_generic_kernel, grid, block, smem, 0, A);
@@ -2006,7 +2151,7 @@ extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *point
   with_value(QueryLayouts{}, code, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH,
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, false,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_kernel<D>, smem);
                        hipLaunchKernelGGL(exact_scan_kernel<D>, grid, block, smem, 0, A);
@@ -2042,8 +2187,8 @@ extern "C" int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *
 extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t *ids_dev,
                                         ftype *dists_dev) {
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  return annhip_exact_knn(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias, ids_dev,
-                          dists_dev);
+  return annhip_exact_knn_filtered(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
+                                   ix->filter, ids_dev, dists_dev);
 }
 
 // ----------------------------------------------------------------------------- precomp

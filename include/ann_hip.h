@@ -76,6 +76,30 @@ int annhip_index_set_probe(annhip_index *ix, int pair_bits);
 int annhip_index_probe(const annhip_index *ix);
 int annhip_probe_bits(annhip_index *ix, void *hip_stream, size_t ycnt, const ftype *y_dev, uint32_t *codes_dev,
                       uint8_t *pbits_dev);
+/* Allow-list row filter of fixed mode (default: none).  Format: uint32_t bits[ceil(n/32)]; row i is allowed iff
+ * bits[i >> 5] >> (i & 31) & 1; bits at or beyond n are ignored.  With a filter set, annhip_query / annhip_query_on /
+ * annhip_stream_* return fixed mode's result with "valid id" read as "id < n, allowed, and not the query itself when
+ * aliased": stage 1 = the k smallest distinct (distance, id) keys among the allowed valid ids of the probed buckets (with
+ * pair bits b the same buckets as without a filter); stage 2 considers the stage-1 results and the ALLOWED graph
+ * neighbours of those results (no traversal through disallowed rows); (n, +inf) where fewer than k candidates exist.  An
+ * all-ones filter returns exactly the unfiltered result, bit for bit.  The bit test happens before a row is fetched: a
+ * disallowed row costs 4 bytes of bitmap, not a row.  Composes with annhip_index_set_probe, annhip_index_set_rows, alias,
+ * workspaces and the host stream; the annhip_sh_* staged calls, precomp, the recall scorer and query_gpu never see it.
+ * annhip_index_set_filter: bits == NULL clears the filter (always accepted, returns 0).  Otherwise the index takes its OWN
+ * copy of ceil(n/32) words (bits_on_device: device or host pointer; the caller's buffer is not borrowed), freed by
+ * annhip_index_destroy.  Synchronous, on the null stream: device words written on another stream (annhip_filter_pack's
+ * hip_stream) must be complete -- synchronise that stream -- before this call.  The caller must not change the filter while batches on this index are in flight.
+ * Returns 0; -1 with one line on stderr and the setting unchanged while fixed mode is off (a parity-mode query that
+ * silently returned filtered-out rows would be worse than a refusal) and for an index that does not hold rows [0, n) on
+ * this device (resharded).  annhip_index_set_fixed(ix, 0) and annhip_index_reshard drop a filter that is set.
+ * annhip_index_filter_count: the allowed rows among [0, n), counted when the filter was set; -1 when none is set.
+ * annhip_filter_pack: one small kernel on hip_stream, u8 flags_dev[n] (non-zero = allowed: what a torch bool tensor holds)
+ * -> bits_dev[ceil(n/32)], the tail bits of the last word zero; returns 0.
+ * annhip_stats out[2] counts, with a filter, only the allowed ids handed to the gather: the sum over the probed buckets
+ * of allowed valid ids, repeats across tries counted, the query itself counted when it is allowed. */
+int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, int bits_on_device);
+long long annhip_index_filter_count(const annhip_index *ix);
+int annhip_filter_pack(size_t n, const uint8_t *flags_dev, uint32_t *bits_dev, void *hip_stream);
 /* Opt-in binary16 point rows (default ANNHIP_ROWS_NATIVE = the reference's results, bit for bit).  With ANNHIP_ROWS_F16,
  * annhip_query / annhip_query_on / annhip_query_slice / annhip_stream_* on this index return exactly what the reference
  * returns for query(save, h(P), y), where h(P) is the point matrix rounded to IEEE binary16 (round to nearest even;
@@ -332,12 +356,19 @@ void annhip_recall_ranks_host(size_t n, size_t d, size_t k, const ftype *points,
  * Device pointers; synchronous; 0 = done. */
 int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
                      int self, size_t *ids_dev, ftype *dists_dev);
+/* annhip_exact_knn over the ALLOWED rows only (bits_dev: device bitmap in annhip_index_set_filter's format): the same
+ * arithmetic, the same (distance, id) order, the same refusals (k > n - self is refused as before, whatever the bitmap
+ * holds).  A query with fewer than k allowed rows gets (n, +inf) in the tail.  bits_dev == NULL behaves as
+ * annhip_exact_knn. */
+int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                              int self, const uint32_t *bits_dev, size_t *ids_dev, ftype *dists_dev);
 /* The same with HOST pointers in and out, for plain-C drivers. */
 int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
                           int self, size_t *ids, ftype *dists);
 /* The same over the rows an index already holds, with the index's own k; alias as in annhip_query (query q leaves out
  * point q).  Always reads the NATIVE rows, whatever annhip_index_set_rows says.  An index that does not hold rows [0, n)
- * (a resharded one) is refused with a non-zero return code. */
+ * (a resharded one) is refused with a non-zero return code.  Honours the index's allow list when one is set
+ * (annhip_index_set_filter): ground truth and query share one allowed set. */
 int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
                              size_t *ids_dev, ftype *dists_dev);
 

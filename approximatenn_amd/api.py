@@ -249,14 +249,43 @@ def _pack_allow_dev(lib, allow, n):
     return bits
 
 
-def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, allow=None):
+def _words_dev(words, length, device, what):
+    """32-bit words for the tag calls -> an int32 device tensor [length] (keep it alive for the call): a numpy uint32
+    array (copied to the device) or a torch int32 device tensor (its bits taken as they are).  ValueError for anything
+    else, a wrong dtype or a wrong length."""
+    import torch
+    if isinstance(words, np.ndarray):
+        if words.dtype != np.uint32 or words.shape != (length,):
+            raise ValueError("%s must be uint32 of length %d" % (what, length))
+        return torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(device)
+    if (not isinstance(words, torch.Tensor) or not words.is_cuda or words.dtype != torch.int32
+            or tuple(words.shape) != (length,)):
+        raise ValueError("%s must be a numpy uint32 array or an int32 device tensor of length %d" % (what, length))
+    return words.contiguous()
+
+
+def _where_dev(where, Q, device):
+    """where = (qmask, qvalue), each as _words_dev takes it -> two int32 device tensors [Q]: query q's predicate is
+    (tags[i] & qmask[q]) == qvalue[q]."""
+    if not isinstance(where, (tuple, list)) or len(where) != 2:
+        raise ValueError("where must be a pair (qmask, qvalue)")
+    return _words_dev(where[0], Q, device, "where[0] (qmask)"), _words_dev(where[1], Q, device, "where[1] (qvalue)")
+
+
+def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, allow=None, tags=None, where=None):
     """annhip_exact_knn: torch device tensors points [n,d], y [Q,d] -> (ids int64 [Q,k], sq dists [Q,k]): the exact k
     nearest rows of every query, ordered by (distance, id), distances bit-identical to the query path's (include/ann_hip.h).
     self_exclude: query q leaves out point q.  Precision from the dtype.  ValueError where the library refuses (k outside
     1..1024 or larger than the rows on offer) and for tensors of mixed or unsupported dtype; the outputs are then untouched.
     allow: a bool device tensor [n] -- annhip_exact_knn_filtered: only rows with allow[i] set compete; a query with fewer
-    than k of them gets (n, +inf) in the tail."""
+    than k of them gets (n, +inf) in the tail.
+    tags + where: annhip_exact_knn_tagged -- tags: the rows' 32-bit tag words (numpy uint32 [n] or int32 device tensor [n]),
+    where = (qmask, qvalue) (numpy uint32 [Q] or int32 device tensors [Q]): row i competes for query q iff
+    (tags[i] & qmask[q]) == qvalue[q]; allow may be given too and is ANDed with that test.  One of the two without the
+    other is a ValueError."""
     import torch
+    if (tags is None) != (where is None):
+        raise ValueError("exact_knn: tags and where=(qmask, qvalue) go together")
     if points.dtype != y.dtype or points.dtype not in (torch.float32, torch.float64):
         raise ValueError("exact_knn: points and y must both be float32 or both float64")
     if points.dim() != 2 or y.dim() != 2 or points.shape[1] != y.shape[1]:
@@ -270,6 +299,17 @@ def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, al
     ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=y.device)
     dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=y.dtype, device=y.device)
     assert ids.is_contiguous() and dists.is_contiguous() and ids.dtype == torch.int64 and dists.dtype == y.dtype
+    if tags is not None:
+        tg = _words_dev(tags, points.shape[0], y.device, "tags")
+        qm, qv = _where_dev(where, Q, y.device)
+        bits = _pack_allow_dev(lib, allow, points.shape[0]) if allow is not None else None
+        torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+        rc = lib.annhip_exact_knn_tagged(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(),
+                                         int(bool(self_exclude)), tg.data_ptr(), bits.data_ptr() if bits is not None else None,
+                                         qm.data_ptr(), qv.data_ptr(), ids.data_ptr(), dists.data_ptr())
+        if rc != 0:
+            raise ValueError("annhip_exact_knn_tagged refused n=%d k=%d self_exclude=%r" % (points.shape[0], k, bool(self_exclude)))
+        return ids, dists
     if allow is not None:
         bits = _pack_allow_dev(lib, allow, points.shape[0])
         rc = lib.annhip_exact_knn_filtered(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(),
@@ -428,6 +468,37 @@ class Index:
         c = int(self.lib.annhip_index_filter_count(self.h))
         return None if c < 0 else c
 
+    def set_tags(self, tags):
+        """annhip_index_set_tags: give every row a 32-bit tag word for query(where=...) and exact_query(where=...).  tags:
+        None (clear), a numpy uint32 array [n], or a torch int32 device tensor [n] whose bits are taken as they are; the
+        index keeps its own copy.  ValueError for a wrong length or dtype and where the library refuses (a resharded
+        index); the setting is then unchanged.  Tags are row attributes: fixed mode need not be on, set_fixed(False)
+        keeps them, reshard drops them, and no query without where= reads them.  Do not change them while batches are
+        in flight."""
+        import torch
+        if tags is None:
+            self.lib.annhip_index_set_tags(self.h, None, 0)
+            return
+        if isinstance(tags, np.ndarray):
+            if tags.dtype != np.uint32 or tags.shape != (self.n,):
+                raise ValueError("tags must be uint32 of length n = %d" % self.n)
+            host = np.ascontiguousarray(tags)
+            rc = self.lib.annhip_index_set_tags(self.h, host.ctypes.data, 0)
+        else:
+            if (not isinstance(tags, torch.Tensor) or not tags.is_cuda or tags.dtype != torch.int32
+                    or tuple(tags.shape) != (self.n,)):
+                raise ValueError("tags must be a numpy uint32 array or an int32 device tensor of length n = %d" % self.n)
+            dev = tags.contiguous()
+            torch.cuda.current_stream(dev.device).synchronize()  # the copy runs on the null stream
+            rc = self.lib.annhip_index_set_tags(self.h, dev.data_ptr(), 1)
+        if rc != 0:
+            raise ValueError("annhip_index_set_tags refused (a resharded index)")
+
+    @property
+    def has_tags(self):
+        """annhip_index_has_tags: True while the index holds tag words."""
+        return bool(self.lib.annhip_index_has_tags(self.h))
+
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
     # the names an index of each precision knows: every library serves its own narrow row type (ANNHIP_ROWS_F32 = 2)
     ROWS_BY_PREC = {"f32": ROWS, "f64": {"native": 0, "f32": 2}}
@@ -453,12 +524,32 @@ class Index:
         self._workspaces = getattr(self, "_workspaces", []) + [ws]
         return ws
 
-    def query(self, y, alias=False, mode=0, out_ids=None, out_dists=None, ws=None, stream=None):
+    def query(self, y, alias=False, mode=0, out_ids=None, out_dists=None, ws=None, stream=None, where=None):
         """annhip_query / annhip_query_on: y torch tensor [Q,d] on the device -> (ids int64 [Q,k], sq dists [Q,k], n_exact).
-        ws + stream (a torch.cuda.Stream): run this batch on its own workspace and stream so that it can overlap others."""
+        ws + stream (a torch.cuda.Stream): run this batch on its own workspace and stream so that it can overlap others.
+        where = (qmask, qvalue), numpy uint32 [Q] or torch int32 device tensors [Q]: annhip_query_tagged -- fixed mode
+        with row i competing for query q iff (tags[i] & qmask[q]) == qvalue[q] (set_tags; the index's filter applies as
+        well).  It runs on `stream` (the null stream when none is given) and `ws` (the index's own when none is given).
+        ValueError for a wrong shape or dtype and where the library refuses (fixed mode off, no tags); nothing is
+        launched then and the outputs are untouched.  where=None is the untagged call."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if where is not None:
+            qm, qv = _where_dev(where, Q, y.device)
+            if not self.has_tags:
+                raise ValueError("query(where=...): the index has no tags (Index.set_tags)")
+            ids = out_ids if out_ids is not None else torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
+            dists = out_dists if out_dists is not None else torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
+            if stream is not None and torch.cuda.current_stream(y.device) != stream:
+                stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate arrays were made on that one
+            nex = self.lib.annhip_query_tagged(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
+                                               int(alias), qm.data_ptr(), qv.data_ptr(), ids.data_ptr(), dists.data_ptr())
+            if nex == -2:
+                raise ValueError("annhip_query_tagged refused (fixed mode off, or no tags)")
+            if stream is not None:  # the arrays may be freed once this call returns: keep them until the batch has read them
+                qm.record_stream(stream), qv.record_stream(stream)
+            return ids, dists, nex
         ids = out_ids if out_ids is not None else torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
         dists = out_dists if out_dists is not None else torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
         if ws is None and stream is None:
@@ -468,15 +559,28 @@ class Index:
                                            int(alias), mode, ids.data_ptr(), dists.data_ptr())
         return ids, dists, nex
 
-    def exact_query(self, y, alias=False):
+    def exact_query(self, y, alias=False, where=None):
         """annhip_index_exact_query: the exact k nearest of the index's (native) rows for y [Q,d], k = the index's k ->
         (ids int64 [Q,k], sq dists [Q,k]), ordered by (distance, id).  alias: query q leaves out point q.  ValueError where
-        the library refuses (a resharded index)."""
+        the library refuses (a resharded index).  where = (qmask, qvalue) as in query(): annhip_index_exact_query_tagged,
+        the exact neighbours among the rows that pass query q's tag test (and the index's filter); ValueError for a wrong
+        shape or dtype and for an index without tags."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if where is not None:
+            qm, qv = _where_dev(where, Q, y.device)
+            if not self.has_tags:
+                raise ValueError("exact_query(where=...): the index has no tags (Index.set_tags)")
         ids = torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
         dists = torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
+        if where is not None:
+            torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+            if self.lib.annhip_index_exact_query_tagged(self.h, Q, y.data_ptr(), int(bool(alias)), qm.data_ptr(), qv.data_ptr(),
+                                                        ids.data_ptr(), dists.data_ptr()) != 0:
+                raise ValueError("annhip_index_exact_query_tagged refused this index (no tags, resharded, or k larger than "
+                                 "the rows on offer)")
+            return ids, dists
         if self.lib.annhip_index_exact_query(self.h, Q, y.data_ptr(), int(bool(alias)), ids.data_ptr(), dists.data_ptr()) != 0:
             raise ValueError("annhip_index_exact_query refused this index (resharded, or k larger than the rows on offer)")
         return ids, dists

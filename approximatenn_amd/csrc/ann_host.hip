@@ -27,6 +27,7 @@
 #include "ann_recall_kernels.h"
 #include "ann_exact_kernels.h"
 #include "ann_filter_kernels.h"
+#include "ann_tag_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -318,6 +319,7 @@ struct annhip_index {
   RN *d_points_h = NULL;          // narrow copy of the rows (made on the first ANNHIP_ROWS_NARROW, kept until destroy/reshard)
   u32 *filter = NULL;             // annhip_index_set_filter: the index's copy of the allow list, u32[ceil(n / 32)] (NULL = none)
   long long filter_count = -1;    // allowed rows among [0, n), taken when the filter was set (-1 = no filter)
+  u32 *tags = NULL;               // annhip_index_set_tags: the index's copy of the rows' tag words, u32[n] (NULL = none)
 };
 
 static QParams make_params(const annhip_index *ix) {
@@ -438,6 +440,28 @@ extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) {
     drop_filter(ix);
   }
 }
+// Row tags (annhip_index_set_tags): attributes of the rows, read by annhip_query_tagged and
+// annhip_index_exact_query_tagged only.  Contract: include/ann_hip.h.  Kernels: ann_tag_kernels.h.
+static void drop_tags(annhip_index *ix) {
+  if (ix->tags) HIPCHECK(hipFree(ix->tags));
+  ix->tags = NULL;
+}
+extern "C" int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int tags_on_device) {
+  if (!tags) {
+    if (ix->tags) HIPCHECK(hipDeviceSynchronize());
+    drop_tags(ix);
+    return 0;
+  }
+  if (ix->lo != 0 || ix->hi != ix->n) {
+    fprintf(stderr, "annhip_index_set_tags: the index does not hold rows [0, n) on this device (resharded)\n");
+    return -1;
+  }
+  HIPCHECK(hipDeviceSynchronize());
+  if (!ix->tags) ix->tags = dev_alloc<u32>(ix->n);
+  HIPCHECK(hipMemcpy(ix->tags, tags, sizeof(u32) * ix->n, tags_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  return 0;
+}
+extern "C" int annhip_index_has_tags(const annhip_index *ix) { return ix->tags ? 1 : 0; }
 // Contract: include/ann_hip.h.  Kernels: ann_filter_kernels.h.
 extern "C" int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, int bits_on_device) {
   if (!bits) {
@@ -591,6 +615,7 @@ extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points
   HIPCHECK(hipDeviceSynchronize());
   drop_half_rows(ix);  // narrow rows are for the whole index on one device: a resharded index reads native rows
   drop_filter(ix);     // ... and so is the allow list
+  drop_tags(ix);       // ... and the rows' tags
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -605,6 +630,7 @@ extern "C" void annhip_index_destroy(annhip_index *ix) {
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   drop_half_rows(ix);
   drop_filter(ix);
+  drop_tags(ix);
   for (u32 *t : ix->d_tabs)
     if (t) HIPCHECK(hipFree(t));
   for (uint2 *sg : ix->d_segs)
@@ -1022,11 +1048,18 @@ static void launch_stage1_probe(annhip_index *ix, const QParams &P, size_t Q, co
   ix->s1_launches += 1;
 }
 
+// The per-query tag predicate of one annhip_query_tagged call (ann_tag_kernels.h): the rows' tag words and the batch's
+// (mask, value) arrays, all on the device.
+struct TagQuery {
+  const u32 *tags, *qmask, *qvalue;
+};
+
 // Stage 1 of fixed mode with an allow list (annhip_index_set_filter; ann_filter_kernels.h): launch_stage1_probe's shape
-// for every pair-bit setting, pb = 0 included (1 + ds runs per try, no ranked bits).
+// for every pair-bit setting, pb = 0 included (1 + ds runs per try, no ranked bits).  tq: annhip_query_tagged's stage 1,
+// the same shape with stage1_tag_kernel (bits may then be NULL).
 static void launch_stage1_filter(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
                                  const unsigned char *pbits, int pb, const u32 *bits, FT *cand_d, u32 *cand_i, u32 *nvt,
-                                 u32 *nvo, hipStream_t s) {
+                                 u32 *nvo, hipStream_t s, const TagQuery *tq = NULL) {
   if (!Q) return;
   const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
   size_t slots = 0;
@@ -1053,6 +1086,12 @@ static void launch_stage1_filter(annhip_index *ix, const QParams &P, size_t Q, c
         constexpr int D = decltype(dd)::value;
         constexpr bool SG = decltype(sg)::value;
         using RT = typename decltype(rt)::type;
+        if (tq) {
+          allow_lds(stage1_tag_kernel<D, SG, RT>, smem);
+          hipLaunchKernelGGL((stage1_tag_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
+                             pb, rpt, tq->tags, bits, tq->qmask, tq->qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
+          return;
+        }
         allow_lds(stage1_filter_kernel<D, SG, RT>, smem);
         hipLaunchKernelGGL((stage1_filter_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
                            pb, rpt, bits, K1, cap, cand_d, cand_i, nvt, nvo);
@@ -1220,9 +1259,10 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
                                         const u32 *top_i, const FT *top_d, u32 *out32, size_t *out64, FT *out_d,
                                         DevBuf &flist, u32 *d_fcount, DevBuf &r2i, DevBuf &r2d,
                                         unsigned long long *exact_total, unsigned long long *rows_ctr, hipStream_t s,
-                                        const u32 *filter = NULL) {  // filter: fixed mode's allow list (stage2_filter_kernel)
+                                        const u32 *filter = NULL, const TagQuery *tq = NULL) {
+  // filter: fixed mode's allow list (stage2_filter_kernel); tq: a tagged query's predicate (stage2_tag_kernel)
   if (!nq) return true;
-  if (filter && !P.fixed) die("stage2_select_with_fallback: an allow list needs fixed mode");
+  if ((filter || tq) && !P.fixed) die("stage2_select_with_fallback: an allow list or a tag predicate needs fixed mode");
   const int K1 = P.k + 1, W = 4, cap = stage1_cap(W, K1);
   const u32 P2 = (P.L2 < 16 || P.fixed) ? P.L2 : (u32)1 << ann_lg(P.L2);
   size_t smem = sizeof(Key) * (size_t)W * cap + 2 * sizeof(Key) * (size_t)W * K1 + sizeof(Key) * (size_t)P.k +
@@ -1240,6 +1280,13 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
         constexpr int D = decltype(dd)::value;
         using RT = typename decltype(rt)::type;
         using TT = std::remove_pointer_t<decltype(out)>;
+        if (tq) {
+          allow_lds((stage2_tag_kernel<D, TT, RT>), smem);
+          hipLaunchKernelGGL((stage2_tag_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
+                             top_i, top_d, tq->tags, filter, tq->qmask, tq->qvalue, P2, K1, cap, out, out_d, fl, d_fcount,
+                             exact_total, rows_ctr, xbase);
+          return;
+        }
         if (filter) {
           allow_lds((stage2_filter_kernel<D, TT, RT>), smem);
           hipLaunchKernelGGL((stage2_filter_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
@@ -1365,7 +1412,9 @@ static size_t codes_needed(const annhip_index *ix, size_t Q) {
 // codes_ext points at the slice's first query (annhip_query_slice).
 static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
                        int mode, size_t *ids_dev, ftype *dists_dev, int codes_ready = 0, const u32 *codes_ext = NULL,
-                       size_t qstride = 0) {  // codes_ready: 1 = ws.codes holds the batch's codes, 2 = and ws.d_fcount has been reset
+                       size_t qstride = 0, const TagQuery *tq = NULL) {
+  // codes_ready: 1 = ws.codes holds the batch's codes, 2 = and ws.d_fcount has been reset
+  // tq: annhip_query_tagged (fixed mode only, checked there): the tag family of stage 1 and stage 2
   if (!Q) return 0;
   if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
   const QParams P = query_params(ix);
@@ -1409,8 +1458,8 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
     nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
     u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-    if (ix->filter)  // allow list: one kernel family for every pair-bit setting (b = 0: no ranked bits)
-      launch_stage1_filter(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s);
+    if (ix->filter || tq)  // allow list, tag predicate: one kernel family each for every pair-bit setting (b = 0: no ranked bits)
+      launch_stage1_filter(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s, tq);
     else if (probing) launch_stage1_probe(ix, P, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
     else launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
     seg_mark(ix, marks, s);
@@ -1420,7 +1469,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     seg_mark(ix, marks, s);
     FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * k);
     if (!stage2_select_with_fallback(P, Q, y, alias, 0, Q, top_i, top_d, NULL, ids_dev, out_d, ws.flist, ws.d_fcount, ws.r2i,
-                                     ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter))
+                                     ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter, tq))
       die("fixed mode: stage-2 shape not supported");
     seg_mark(ix, marks, s);
     seg_mark(ix, marks, s);
@@ -1560,6 +1609,21 @@ extern "C" void annhip_workspace_destroy(annhip_workspace *ws) {
 extern "C" long annhip_query_on(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t Q, const ftype *y_dev,
                                 int alias, int mode, size_t *ids_dev, ftype *dists_dev) {
   return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, mode, ids_dev, dists_dev);
+}
+
+// Contract: include/ann_hip.h.  A refusal launches nothing and leaves the outputs untouched.
+extern "C" long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t Q, const ftype *y_dev,
+                                    int alias, const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                                    ftype *dists_dev) {
+  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
+                    : !ix->tags ? "the index has no tags (annhip_index_set_tags)"
+                    : !qmask_dev || !qvalue_dev ? "qmask_dev and qvalue_dev must both be given" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_query_tagged: %s\n", why);
+    return -2;
+  }
+  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
 }
 
 extern "C" long annhip_query_slice(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, size_t q_lo, size_t nq,
@@ -2039,7 +2103,9 @@ static int exact_check(size_t n, size_t d, size_t k, int self) {
 // smem, args) starts the scan of one chunk of queries.  prefetch: the kernel moves the next tile through registers.
 template <typename Launch>
 static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
-                     FT *dists_dev, bool generic, int max_waves, bool prefetch, bool filtered, Launch &&launch) {
+                     FT *dists_dev, bool generic, int max_waves, bool prefetch, int filtered, Launch &&launch) {
+  // filtered: 0 = every row, 1 = allow list (ann_filter_kernels.h), 2 = tag predicate, with or without an allow list
+  // (ann_tag_kernels.h)
   // LDS of a workgroup: the row tile, then per wave the selection buffers (and the query + tree scratch of the any-d path)
   const size_t row_bytes = d * sizeof(FT);
   const size_t cap = k + ANN_EX_SLACK;
@@ -2050,13 +2116,15 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
   auto tile_rows_of = [&](size_t W, bool pf) {
     return std::max<size_t>(1, (pf ? (size_t)ANN_EX_PF * 64 * W * 16 : (size_t)ANN_EX_GEN_TILE_BYTES) / row_bytes);
   };
-  auto smem_of = [&](size_t W, bool pf) {  // (filtered: the tile's words of the allow list behind the waves' buffers)
-    return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +
+  auto smem_of = [&](size_t W, bool pf) {  // (filtered: the tile's words of the allow list behind the waves' buffers,
+    return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +  // tagged: its tag words before them)
+           (filtered == 2 ? sizeof(u32) * tile_rows_of(W, pf) : 0) +
            (filtered ? sizeof(u32) * ANN_EX_TBITS(tile_rows_of(W, pf)) : 0);
   };
   size_t W = (size_t)max_waves;
   while (W > 1 && smem_of(W, prefetch) > ANN_EX_LDS_BUDGET) W--;
   if (prefetch && row_bytes > (size_t)ANN_EX_PF * 64 * W * 16) prefetch = false;  // one row is more than the threads hold
+  if (prefetch && filtered == 2 && tile_rows_of(W, true) > 64 * W) prefetch = false;  // ... or more tags: one per thread
   const size_t smem = smem_of(W, prefetch);
   if (smem > 160 * 1024) return exact_refuse("row too long for the LDS of one CU");
   const size_t tile_rows = tile_rows_of(W, prefetch);
@@ -2115,7 +2183,7 @@ extern "C" int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const fty
   const u32 *bits = bits_dev;
   const int code = layout_code(d);
   if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, true,
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 1,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_generic_filtered_kernel, smem);
                        hipLaunchKernelGGL(exact_scan_generic_filtered_kernel, grid, block, smem, 0, A, bits);
@@ -2124,10 +2192,41 @@ extern "C" int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const fty
   with_value(QueryLayouts{}, code, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, true,
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 1,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_filtered_kernel<D>, smem);
                        hipLaunchKernelGGL(exact_scan_filtered_kernel<D>, grid, block, smem, 0, A, bits);
+                     });
+  });
+  return rc;
+}
+
+extern "C" int annhip_exact_knn_tagged(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                                       int self, const uint32_t *tags_dev, const uint32_t *bits_dev,
+                                       const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                                       ftype *dists_dev) {
+  if (!tags_dev || !qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  if (!ycnt) return 0;
+  gpu_init();
+  const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  const ExTagArgs G{tags_dev, bits_dev, qmask_dev, qvalue_dev};
+  const int code = layout_code(d);
+  if (layout_is_generic(code))
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 2,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_generic_tag_kernel, smem);
+                       hipLaunchKernelGGL(exact_scan_generic_tag_kernel, grid, block, smem, 0, A, G);
+                     });
+  int rc = 1;
+  with_value(QueryLayouts{}, code, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D != 0 && !OcCode<D>::GEN)
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 2,
+                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
+                       allow_lds(exact_scan_tag_kernel<D>, smem);
+                       hipLaunchKernelGGL(exact_scan_tag_kernel<D>, grid, block, smem, 0, A, G);
                      });
   });
   return rc;
@@ -2142,7 +2241,7 @@ extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *point
   FT *dd = reinterpret_cast<FT *>(dists_dev);
   const int code = layout_code(d);
   if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, false,
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 0,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_generic_kernel, smem);
                        hipLaunchKernelGGL(exact_scan_generic_kernel, grid, block, smem, 0, A);
@@ -2151,7 +2250,7 @@ extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *point
   with_value(QueryLayouts{}, code, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, false,
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 0,
                      [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
                        allow_lds(exact_scan_kernel<D>, smem);
                        hipLaunchKernelGGL(exact_scan_kernel<D>, grid, block, smem, 0, A);
@@ -2189,6 +2288,15 @@ extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const fty
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   return annhip_exact_knn_filtered(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
                                    ix->filter, ids_dev, dists_dev);
+}
+
+extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
+                                               const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                                               ftype *dists_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
+  return annhip_exact_knn_tagged(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
+                                 ix->tags, ix->filter, qmask_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
 // ----------------------------------------------------------------------------- precomp

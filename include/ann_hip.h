@@ -100,6 +100,36 @@ int annhip_probe_bits(annhip_index *ix, void *hip_stream, size_t ycnt, const fty
 int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, int bits_on_device);
 long long annhip_index_filter_count(const annhip_index *ix);
 int annhip_filter_pack(size_t n, const uint8_t *flags_dev, uint32_t *bits_dev, void *hip_stream);
+/* Per-query tag predicates of fixed mode (default: no tags).  The allow list above is one set for the whole index and
+ * every query of a batch; tags let every query of a batch carry its own predicate.  Rows carry a 32-bit tag word
+ * (uint32_t tags[n]), every query a (mask, value) pair (uint32_t qmask[ycnt], qvalue[ycnt]), and row i competes for query
+ * q iff (tags[i] & qmask[q]) == qvalue[q].  Examples: tenant equality (mask 0xFFFFFFFF), equality on a packed field
+ * (tenant in the low 24 bits, flags above), "this tenant and not deleted", everything (mask 0, value 0).  A query with
+ * qvalue & ~qmask != 0 matches nothing.
+ * annhip_index_set_tags: tags == NULL clears the tags (always accepted, returns 0).  Otherwise the index takes its OWN copy
+ * of n words (tags_on_device: device or host pointer), freed by annhip_index_destroy.  Synchronous, on the null stream, as
+ * annhip_index_set_filter is: device words written on another stream must be complete before the call, and the tags must
+ * not change while batches on this index are in flight.  Returns 0; -1 with one line on stderr and the setting unchanged
+ * for an index that does not hold rows [0, n) on this device (resharded).  annhip_index_reshard drops the tags.  Tags are
+ * row attributes, not a filter: they may be set in parity mode, they survive annhip_index_set_fixed(ix, 0), and no
+ * untagged call (annhip_query, annhip_query_on, annhip_stream_*, ...) ever reads them or returns anything else because
+ * they are set.  annhip_index_has_tags: 0 or 1.
+ * annhip_query_tagged: annhip_query_on (ws == NULL = the index's workspace; the stream handled the same way; mode 0) plus
+ * the two device arrays u32[ycnt].  The result is fixed mode's with "valid id" read, for query q, as all of: id < n;
+ * (tags[id] & qmask[q]) == qvalue[q]; allowed by the index's allow list when one is set (both tests apply, ANDed); not the
+ * query itself when aliased.  Stage 1 = the k smallest distinct (distance, id) keys among those ids of the probed buckets
+ * -- the same buckets as without tags, for every pair-bit setting; stage 2 considers the stage-1 results and those of
+ * their graph neighbours that pass the same test; (n, +inf) pads, so a query that matches nothing returns k pads.  The
+ * test happens before a row is fetched: a row that does not match costs its 4-byte id and its 4-byte tag.  Returns 0;
+ * -2, with one line on stderr, nothing launched and the outputs untouched, while fixed mode is off, while the index has
+ * no tags, and when either array is NULL (-1 stays annhip_query_on's "asynchronous" return).  Composes with
+ * annhip_index_set_probe, annhip_index_set_rows, alias, and several workspaces on several streams.  NOT covered:
+ * annhip_stream_*, annhip_sh_*, annhip_query_slice, query_gpu and parity mode take no predicate.
+ * annhip_stats out[2] counts, for a tagged query, the ids handed to the gather: the matching (and allowed) valid ids over
+ * the probed buckets, repeats across tries counted, the query itself counted when it matches.
+ * (annhip_query_tagged is declared below, beside annhip_query_on, where the workspace type is known.) */
+int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int tags_on_device);
+int annhip_index_has_tags(const annhip_index *ix);
 /* Opt-in binary16 point rows (default ANNHIP_ROWS_NATIVE = the reference's results, bit for bit).  With ANNHIP_ROWS_F16,
  * annhip_query / annhip_query_on / annhip_query_slice / annhip_stream_* on this index return exactly what the reference
  * returns for query(save, h(P), y), where h(P) is the point matrix rounded to IEEE binary16 (round to nearest even;
@@ -222,6 +252,9 @@ annhip_workspace *annhip_workspace_create(annhip_index *ix);
 void annhip_workspace_destroy(annhip_workspace *ws);
 long annhip_query_on(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev,
                      int alias, int mode, size_t *ids_dev, ftype *dists_dev);
+/* annhip_query_on with a per-query tag predicate: the contract is with annhip_index_set_tags above. */
+long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                         const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 
 /* Query-sharded ("replica") hosts: every device holds ALL rows and the whole index, and answers a contiguous slice of every
  * batch.  Results depend on the whole batch (query x reads hash codes of other queries), so the codes of all
@@ -362,6 +395,14 @@ int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size
  * annhip_exact_knn. */
 int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
                               int self, const uint32_t *bits_dev, size_t *ids_dev, ftype *dists_dev);
+/* annhip_exact_knn_filtered with a per-query tag predicate (device arrays tags_dev[n], qmask_dev[ycnt], qvalue_dev[ycnt]):
+ * row i competes for query q iff (tags_dev[i] & qmask_dev[q]) == qvalue_dev[q] and, where bits_dev != NULL, row i is
+ * allowed by that bitmap.  The same arithmetic, (distance, id) order and refusals (k > n - self is refused as before,
+ * whatever the tags hold; a NULL tags_dev, qmask_dev or qvalue_dev is refused too).  A query with fewer than k matching
+ * rows gets (n, +inf) in the tail. */
+int annhip_exact_knn_tagged(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                            int self, const uint32_t *tags_dev, const uint32_t *bits_dev /* may be NULL */,
+                            const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 /* The same with HOST pointers in and out, for plain-C drivers. */
 int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
                           int self, size_t *ids, ftype *dists);
@@ -371,6 +412,11 @@ int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, siz
  * (annhip_index_set_filter): ground truth and query share one allowed set. */
 int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
                              size_t *ids_dev, ftype *dists_dev);
+/* annhip_exact_knn_tagged over the index's native rows and its tags (annhip_index_set_tags), honouring the index's allow
+ * list when one is set: the ground truth of annhip_query_tagged.  Non-zero for an index without tags or a resharded one. */
+int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
+                                    const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                                    ftype *dists_dev);
 
 /* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /

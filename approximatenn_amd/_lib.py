@@ -23,7 +23,8 @@ class SaveT(C.Structure):
 
 def build(verbose=False):
     """Compile every HIP extension for gfx950 (hipcc cross-compiles without a GPU)."""
-    cmd = ["make", "-C", CSRC, "all"]
+    # the two precisions are independent translation units of ~15 minutes each: build them side by side
+    cmd = ["make", "-j4", "-C", CSRC, "all"]
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.check_call(cmd)
@@ -86,6 +87,12 @@ def load(prec="f32"):
     lib.annhip_index_has_tags.argtypes = [vp]
     lib.annhip_query_tagged.restype = C.c_long
     lib.annhip_query_tagged.argtypes = [vp, vp, vp, sz, vp, C.c_int, vp, vp, vp, vp]
+    lib.annhip_query_k.restype = C.c_long
+    lib.annhip_query_k.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp]
+    lib.annhip_index_max_query_k.restype = sz
+    lib.annhip_index_max_query_k.argtypes = [vp]
+    lib.annhip_index_exact_query_k.restype = C.c_int
+    lib.annhip_index_exact_query_k.argtypes = [vp, sz, vp, C.c_int, sz, vp, vp, vp, vp]
     lib.annhip_index_set_rows.restype = C.c_int
     lib.annhip_index_set_rows.argtypes = [vp, C.c_int]
     lib.annhip_index_rows.restype = C.c_int
@@ -197,6 +204,7 @@ EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp
             "annhip_index_set_filter", "annhip_index_filter_count", "annhip_filter_pack", "annhip_exact_knn_filtered",
             "annhip_index_set_tags", "annhip_index_has_tags", "annhip_query_tagged", "annhip_exact_knn_tagged",
             "annhip_index_exact_query_tagged",
+            "annhip_query_k", "annhip_index_max_query_k", "annhip_index_exact_query_k",
             "annhip_index_export", "annhip_index_reshard", "annhip_save_write", "annhip_save_read", "annhip_precomp_index", "annhip_precomp_begin", "annhip_precomp_info", "annhip_precomp_init_merged", "annhip_precomp_hash",
             "annhip_precomp_try", "annhip_precomp_merge", "annhip_precomp_graph", "annhip_precomp_finish", "annhip_query", "annhip_workspace_create", "annhip_workspace_destroy", "annhip_query_on", "annhip_query_slice", "annhip_stream_open", "annhip_stream_submit", "annhip_stream_collect", "annhip_stream_close",
             "annhip_key_bytes", "annhip_stream_create_reserving", "annhip_stream_destroy", "annhip_sh_codes", "annhip_sh_stage1", "annhip_sh_merge_finalize", "annhip_sh_exact1_begin", "annhip_sh_exact1_end", "annhip_sh_stage2",

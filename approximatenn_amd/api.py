@@ -524,17 +524,53 @@ class Index:
         self._workspaces = getattr(self, "_workspaces", []) + [ws]
         return ws
 
-    def query(self, y, alias=False, mode=0, out_ids=None, out_dists=None, ws=None, stream=None, where=None):
+    @staticmethod
+    def _check_k(k):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError("k must be an integer, got %r" % (k,))
+        return int(k)
+
+    @property
+    def max_query_k(self):
+        """annhip_index_max_query_k: the largest k that query(k=...) accepts on this index (at most 1024)."""
+        return int(self.lib.annhip_index_max_query_k(self.h))
+
+    def query(self, y, alias=False, mode=0, out_ids=None, out_dists=None, ws=None, stream=None, where=None, k=None):
         """annhip_query / annhip_query_on: y torch tensor [Q,d] on the device -> (ids int64 [Q,k], sq dists [Q,k], n_exact).
         ws + stream (a torch.cuda.Stream): run this batch on its own workspace and stream so that it can overlap others.
         where = (qmask, qvalue), numpy uint32 [Q] or torch int32 device tensors [Q]: annhip_query_tagged -- fixed mode
         with row i competing for query q iff (tags[i] & qmask[q]) == qvalue[q] (set_tags; the index's filter applies as
         well).  It runs on `stream` (the null stream when none is given) and `ws` (the index's own when none is given).
         ValueError for a wrong shape or dtype and where the library refuses (fixed mode off, no tags); nothing is
-        launched then and the outputs are untouched.  where=None is the untagged call."""
+        launched then and the outputs are untouched.  where=None is the untagged call.
+        k: None = the index's k, the calls above, unchanged.  An integer: annhip_query_k -- fixed mode with the k of this
+        call, 1 <= k <= max_query_k, -> (ids int64 [Q,k], sq dists [Q,k], 0); with or without where=, on `stream` / `ws`
+        as where= is.  ValueError for a bool or a non-integer and where the library refuses (fixed mode off, k out of
+        range, where= without tags, a resharded index); nothing is launched then and the outputs are untouched."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if k is not None:
+            k = self._check_k(k)
+            if k < 1:
+                raise ValueError("query(k=...): k must be at least 1")
+            qm = qv = None
+            if where is not None:
+                qm, qv = _where_dev(where, Q, y.device)
+            ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=y.device)
+            dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=y.dtype, device=y.device)
+            assert tuple(ids.shape) == (Q, k) and tuple(dists.shape) == (Q, k) and ids.is_contiguous() and dists.is_contiguous()
+            if qm is not None and stream is not None and torch.cuda.current_stream(y.device) != stream:
+                stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate arrays were made on that one
+            rc = self.lib.annhip_query_k(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
+                                         int(alias), k, qm.data_ptr() if qm is not None else None,
+                                         qv.data_ptr() if qv is not None else None, ids.data_ptr(), dists.data_ptr())
+            if rc == -2:
+                raise ValueError("annhip_query_k refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
+                                 % (k, self.max_query_k))
+            if qm is not None and stream is not None:
+                qm.record_stream(stream), qv.record_stream(stream)
+            return ids, dists, rc
         if where is not None:
             qm, qv = _where_dev(where, Q, y.device)
             if not self.has_tags:
@@ -559,15 +595,34 @@ class Index:
                                            int(alias), mode, ids.data_ptr(), dists.data_ptr())
         return ids, dists, nex
 
-    def exact_query(self, y, alias=False, where=None):
+    def exact_query(self, y, alias=False, where=None, k=None):
         """annhip_index_exact_query: the exact k nearest of the index's (native) rows for y [Q,d], k = the index's k ->
         (ids int64 [Q,k], sq dists [Q,k]), ordered by (distance, id).  alias: query q leaves out point q.  ValueError where
         the library refuses (a resharded index).  where = (qmask, qvalue) as in query(): annhip_index_exact_query_tagged,
         the exact neighbours among the rows that pass query q's tag test (and the index's filter); ValueError for a wrong
-        shape or dtype and for an index without tags."""
+        shape or dtype and for an index without tags.
+        k: None = the index's k, the calls above.  An integer: annhip_index_exact_query_k, the exact k nearest ->
+        [Q,k] tensors; ValueError for a bool or a non-integer and where the library refuses (k outside 1..1024,
+        k > n - alias, a resharded index, where= without tags)."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if k is not None:
+            k = self._check_k(k)
+            if k < 1:
+                raise ValueError("exact_query(k=...): k must be in 1..1024")
+            qm = qv = None
+            if where is not None:
+                qm, qv = _where_dev(where, Q, y.device)
+            ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
+            dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
+            torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+            if self.lib.annhip_index_exact_query_k(self.h, Q, y.data_ptr(), int(bool(alias)), k,
+                                                   qm.data_ptr() if qm is not None else None,
+                                                   qv.data_ptr() if qv is not None else None, ids.data_ptr(), dists.data_ptr()) != 0:
+                raise ValueError("annhip_index_exact_query_k refused k=%d (k outside 1..1024 or larger than the rows on offer, "
+                                 "no tags, or a resharded index)" % k)
+            return ids, dists
         if where is not None:
             qm, qv = _where_dev(where, Q, y.device)
             if not self.has_tags:

@@ -28,6 +28,7 @@
 #include "ann_exact_kernels.h"
 #include "ann_filter_kernels.h"
 #include "ann_tag_kernels.h"
+#include "ann_kq_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -1626,6 +1627,132 @@ extern "C" long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void
   return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
 }
 
+// ----------------------------------------------------------------------------- query with a per-call k (annhip_query_k)
+// Contract: include/ann_hip.h.  kg = ix->k (graph width), kq = the k of the call.  Stage 1 does not depend on k in fixed
+// mode (P1 = Lc1 = L1) and none of its kernels reads QParams::k: the existing launchers run on a QParams copy whose k is
+// kq, which sizes K1, cap and the LDS.  Stage 2 is stage2_kq_kernel (ann_kq_kernels.h) on the index's own QParams.
+static size_t stage2_kq_lds_bytes(const QParams &P, int W, int K1, int cap, size_t kq) {
+  size_t b = sizeof(Key) * (size_t)W * cap + 2 * sizeof(Key) * (size_t)W * K1 + sizeof(Key) * kq +
+             sizeof(u32) * (size_t)W * ANN_S1_CHUNK + sizeof(int) * (size_t)W + sizeof(u32) * 4;
+  b = (b + 15) & ~(size_t)15;
+  if (d_needs_lds_row(P.d)) b += sizeof(FT) * (size_t)P.d * (1 + W);
+  return b;
+}
+#define ANN_KQ_LDS_MAX ((size_t)160 * 1024)  // what allow_lds permits
+// Waves per query of stage 2 for this kq: the most of 4, 2, 1 whose carve-up fits (results do not depend on the count);
+// 0 = none fits.
+static int stage2_kq_waves(const QParams &P, size_t kq) {
+  for (int W = 4; W >= 1; W >>= 1)
+    if (stage2_kq_lds_bytes(P, W, (int)kq + 1, stage1_cap(W, (int)kq + 1), kq) <= ANN_KQ_LDS_MAX) return W;
+  return 0;
+}
+// Does a call with this kq fit?  Stage 1 is judged by the worst of its families at the most waves a launcher takes (4, or
+// ANN_HIP_S1_WAVES) and the most pair bits (d_short): the answer does not depend on the probe, filter or tag settings.
+static bool query_k_fits(const QParams &P, size_t kq) {
+  if (kq < 1 || kq > 1024 || (kq + 1) * ((size_t)P.k + 1) >= 0x7FFFFFFFull) return false;
+  const int K1 = (int)kq + 1, W1 = env().s1_waves ? env().s1_waves : 4, cap1 = stage1_cap(W1, K1);
+  const size_t s1 = std::max(stage1_lds_bytes(P, W1, K1, cap1), stage1_probe_lds_bytes(P, W1, K1, cap1, P.ds));
+  return s1 <= ANN_KQ_LDS_MAX && stage2_kq_waves(P, kq) > 0;
+}
+
+extern "C" size_t annhip_index_max_query_k(const annhip_index *ix) {
+  const QParams P = make_params(ix);
+  size_t lo = 0, hi = 1024;  // the carve-ups grow with kq: the largest kq that fits, by bisection
+  while (lo < hi) {
+    const size_t mid = (lo + hi + 1) / 2;
+    if (query_k_fits(P, mid)) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+static void launch_stage2_kq(const QParams &P, size_t Q, const FT *y, int alias, const u32 *top_i, const FT *top_d, size_t kq,
+                             const u32 *filter, const TagQuery *tq, size_t *out_ids, FT *out_d, unsigned long long *rows_ctr,
+                             hipStream_t s) {
+  if (!Q) return;
+  const int W = stage2_kq_waves(P, kq), K1 = (int)kq + 1, cap = stage1_cap(W, K1);
+  if (W < 1) die("launch_stage2_kq: kq beyond annhip_index_max_query_k");
+  const size_t smem = stage2_kq_lds_bytes(P, W, K1, cap, kq);
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      constexpr int D = decltype(dd)::value;
+      using RT = typename decltype(rt)::type;
+      allow_lds((stage2_kq_kernel<D, size_t, RT>), smem);
+      hipLaunchKernelGGL((stage2_kq_kernel<D, size_t, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, top_i, top_d,
+                         (int)kq, tq ? tq->tags : (const u32 *)NULL, filter, tq ? tq->qmask : (const u32 *)NULL,
+                         tq ? tq->qvalue : (const u32 *)NULL, K1, cap, out_ids, out_d, rows_ctr);
+    });
+  });
+  HIPCHECK(hipGetLastError());
+}
+
+// query_impl's fixed branch with kq in the place of k (the caller has validated everything)
+static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias, size_t kq,
+                         const TagQuery *tq, size_t *ids_dev, ftype *dists_dev) {
+  if (!Q) return 0;
+  if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
+  const QParams P = query_params(ix);
+  QParams P1 = P;  // stage 1's view: k = kq
+  P1.k = (int)kq;
+  if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
+  const FT *y = reinterpret_cast<const FT *>(y_dev);
+  const int K1 = (int)kq + 1;
+  std::vector<hipEvent_t> marks_store, *marks = ix->profile == 1 ? &marks_store : NULL;
+  seg_mark(ix, marks, s);
+  const bool probing = ix->probe > 0;
+  unsigned char *pbits = NULL;
+  u32 *codes = (u32 *)ws.codes.need(sizeof(u32) * Q * P.T);
+  if (probing) {
+    pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
+    launch_codes_probe(P, Q, y, codes, pbits, ix->probe, s, ws.d_fcount);
+  } else {
+    launch_codes(P, Q, y, codes, s, ws.d_fcount);
+  }
+  seg_mark(ix, marks, s);
+  u32 *top_i = (u32 *)ws.top_i.need(sizeof(u32) * Q * kq);
+  FT *top_d = (FT *)ws.top_d.need(sizeof(FT) * Q * kq);
+  FT *cand_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * K1);
+  u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
+  u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
+  u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
+  if (ix->filter || tq)
+    launch_stage1_filter(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s, tq);
+  else if (probing) launch_stage1_probe(ix, P1, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
+  else launch_stage1(ix, P1, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
+  seg_mark(ix, marks, s);
+  hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kq, K1, P.L1, P.P1, cand_d,
+                     cand_i, nvt, top_i, top_d, (int)kq, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
+  HIPCHECK(hipGetLastError());
+  seg_mark(ix, marks, s);
+  FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
+  launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+  seg_mark(ix, marks, s);
+  seg_mark(ix, marks, s);
+  seg_mark(ix, marks, s);
+  if (marks) ix->seg_used.push_back(marks_store);
+  ix->queries += (double)Q;
+  return 0;
+}
+
+// Contract: include/ann_hip.h.  A refusal launches nothing and leaves the outputs untouched; this entry never aborts on
+// what it can refuse.
+extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                               size_t kq, const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                               ftype *dists_dev) {
+  const bool tagged = qmask_dev && qvalue_dev;
+  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
+                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                    : (qmask_dev != NULL) != (qvalue_dev != NULL) ? "qmask_dev and qvalue_dev must both be given, or neither"
+                    : tagged && !ix->tags ? "the index has no tags (annhip_index_set_tags)"
+                    : !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_query_k: %s\n", why);
+    return -2;
+  }
+  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, tagged ? &tq : NULL, ids_dev,
+                      dists_dev);
+}
+
 extern "C" long annhip_query_slice(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, size_t q_lo, size_t nq,
                                    const ftype *y_slice_dev, const uint32_t *codes_all_dev, int alias, size_t *ids_dev,
                                    ftype *dists_dev) {
@@ -2297,6 +2424,19 @@ extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, co
   if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
   return annhip_exact_knn_tagged(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
                                  ix->tags, ix->filter, qmask_dev, qvalue_dev, ids_dev, dists_dev);
+}
+
+// Contract: include/ann_hip.h.  The three exact scans with a k of the call's own; their refusals.
+extern "C" int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
+                                          const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
+                                          ftype *dists_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
+  const ftype *pts = reinterpret_cast<const ftype *>(ix->d_points);
+  if (!qmask_dev) return annhip_exact_knn_filtered(ix->n, ix->d, kq, pts, ycnt, y_dev, alias, ix->filter, ids_dev, dists_dev);
+  if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
+  return annhip_exact_knn_tagged(ix->n, ix->d, kq, pts, ycnt, y_dev, alias, ix->tags, ix->filter, qmask_dev, qvalue_dev, ids_dev,
+                                 dists_dev);
 }
 
 // ----------------------------------------------------------------------------- precomp

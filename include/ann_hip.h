@@ -256,6 +256,35 @@ long annhip_query_on(annhip_index *ix, annhip_workspace *ws, void *hip_stream, s
 long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
                          const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 
+/* A fixed-mode query whose k is chosen by the call.  Let kg be the index's k -- the width of its neighbour graph -- and kq
+ * the k of this call.  annhip_query_k returns, for query q:
+ *   stage 1: the kq smallest distinct (distance, id) keys among the valid ids of the probed buckets over all tries.  The
+ *     buckets are the same as in annhip_query for every pair-bit setting (annhip_index_set_probe), and "valid" is read
+ *     exactly as there: id < n; allowed by the allow list when one is set (annhip_index_set_filter); passing the query's
+ *     tag test when the call is tagged; not the query itself when aliased.
+ *   stage 2: the kq smallest distinct keys among the stage-1 results and the valid graph neighbours graph[p][z], z < kg,
+ *     of the real (id < n) stage-1 results p.  A pad among the stage-1 results contributes nothing.
+ *   output: ids_dev size_t[ycnt][kq], dists_dev ftype[ycnt][kq] (may be NULL), rows ascending by (distance, id), with
+ *     (n, +inf) where fewer exist.
+ * kq == kg returns the bits of today's call: annhip_query / annhip_query_on in fixed mode and, tagged, annhip_query_tagged.
+ * ws and hip_stream behave as in annhip_query_tagged.  qmask_dev and qvalue_dev both NULL: an untagged call; both non-NULL
+ * (u32[ycnt] each): a tagged call, the predicate as in annhip_query_tagged.  Asynchronous; returns 0.  Returns -2, with one
+ * line on stderr, nothing launched and the outputs untouched: while fixed mode is off; for kq == 0 or
+ * kq > annhip_index_max_query_k(ix); when exactly one of the two predicate arrays is given; for a tagged call on an index
+ * without tags; for an index that does not hold rows [0, n) on this device (resharded) -- this entry validates before it
+ * launches and never aborts on any of these.  ycnt == 0 returns 0.  Composes with annhip_index_set_probe,
+ * annhip_index_set_filter, annhip_index_set_rows, alias, and several workspaces on several streams.  NOT covered: parity
+ * mode, annhip_stream_*, annhip_sh_*, annhip_query_slice and query_gpu answer the index's k only; every existing entry
+ * point launches exactly what it launched before.
+ * annhip_index_max_query_k: the largest kq this index accepts -- at most 1024, lower where the LDS carve-up of stage 1
+ * (the worst of its kernel families, at the most waves per query and pair bits they take) or of stage 2 would exceed what
+ * one workgroup may have (160 KB).  It depends on d, tries, d_short and the precision, not on the probe, filter, tag or
+ * row settings; at least 256 for the row lengths the library's register layouts serve.  Stage 2 runs fewer waves per
+ * query for a large kq; results do not depend on the wave count. */
+long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                    size_t kq, const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
+size_t annhip_index_max_query_k(const annhip_index *ix);
+
 /* Query-sharded ("replica") hosts: every device holds ALL rows and the whole index, and answers a contiguous slice of every
  * batch.  Results depend on the whole batch (query x reads hash codes of other queries), so the codes of all
  * ycnt queries must be known everywhere: each device hashes its slice (annhip_sh_codes), ONE all-gather makes
@@ -417,6 +446,13 @@ int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, 
 int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
                                     const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
                                     ftype *dists_dev);
+/* annhip_index_exact_query / annhip_index_exact_query_tagged with a k of the call's own: the exact kq nearest of the
+ * index's native rows, ids_dev size_t[ycnt][kq], dists_dev ftype[ycnt][kq].  Honours the allow list when one is set, and
+ * the tag test when both predicate arrays are given (both NULL: untagged; exactly one: refused).  The refusals of
+ * annhip_exact_knn*: kq outside 1..1024, kq > n - alias, a resharded index, a tagged call on an index without tags --
+ * non-zero, outputs untouched.  The ground truth of annhip_query_k. */
+int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
+                               const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 
 /* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /

@@ -451,13 +451,14 @@ class Index:
         if allow is None:
             self.lib.annhip_index_set_filter(self.h, None, 0)
             return
+        rows = self.n_total  # the built rows and the appended ones: one array serves both
         if isinstance(allow, np.ndarray):
-            if allow.shape != (self.n,):
-                raise ValueError("allow must have length n = %d" % self.n)
+            if allow.shape != (rows,):
+                raise ValueError("allow must have length n_total = %d" % rows)
             bits = pack_allow(allow)
             rc = self.lib.annhip_index_set_filter(self.h, bits.ctypes.data, 0)
         else:
-            bits = _pack_allow_dev(self.lib, allow, self.n)
+            bits = _pack_allow_dev(self.lib, allow, rows)
             rc = self.lib.annhip_index_set_filter(self.h, bits.data_ptr(), 1)
         if rc != 0:
             raise ValueError("annhip_index_set_filter refused (fixed mode off, or a resharded index)")
@@ -479,15 +480,16 @@ class Index:
         if tags is None:
             self.lib.annhip_index_set_tags(self.h, None, 0)
             return
+        rows = self.n_total  # the built rows and the appended ones: one array serves both
         if isinstance(tags, np.ndarray):
-            if tags.dtype != np.uint32 or tags.shape != (self.n,):
-                raise ValueError("tags must be uint32 of length n = %d" % self.n)
+            if tags.dtype != np.uint32 or tags.shape != (rows,):
+                raise ValueError("tags must be uint32 of length n_total = %d" % rows)
             host = np.ascontiguousarray(tags)
             rc = self.lib.annhip_index_set_tags(self.h, host.ctypes.data, 0)
         else:
             if (not isinstance(tags, torch.Tensor) or not tags.is_cuda or tags.dtype != torch.int32
-                    or tuple(tags.shape) != (self.n,)):
-                raise ValueError("tags must be a numpy uint32 array or an int32 device tensor of length n = %d" % self.n)
+                    or tuple(tags.shape) != (rows,)):
+                raise ValueError("tags must be a numpy uint32 array or an int32 device tensor of length n_total = %d" % rows)
             dev = tags.contiguous()
             torch.cuda.current_stream(dev.device).synchronize()  # the copy runs on the null stream
             rc = self.lib.annhip_index_set_tags(self.h, dev.data_ptr(), 1)
@@ -498,6 +500,104 @@ class Index:
     def has_tags(self):
         """annhip_index_has_tags: True while the index holds tag words."""
         return bool(self.lib.annhip_index_has_tags(self.h))
+
+    # ---- appended rows (include/ann_hip.h, "Appended rows of fixed mode: the tail")
+    @property
+    def tail(self):
+        """annhip_index_tail: m, the number of rows appended since the build."""
+        return int(self.lib.annhip_index_tail(self.h))
+
+    @property
+    def n_total(self):
+        """n + tail: the rows a fixed-mode query answers from; ids run over [0, n_total), pads carry n_total."""
+        return self.n + self.tail
+
+    def append(self, rows, tags=None):
+        """annhip_index_append: add rows [count, d] -- a numpy array or a torch device tensor of the index's precision -- to
+        the index's tail; every fixed-mode query scans the tail exactly and merges it into its answer.  tags: the new rows'
+        tag words (numpy uint32 [count] or int32 device tensor [count]), required exactly when the index has tags.  Returns
+        the id of the first new row (n_total before the call).  With an allow list set the new rows are allowed.
+        ValueError for a wrong shape or dtype and where the library refuses (fixed mode off, a resharded index, narrow
+        rows, tags missing or unexpected); nothing changes then.  Do not append while batches are in flight."""
+        import torch
+        first = self.n_total
+        if isinstance(rows, np.ndarray):
+            if rows.ndim != 2 or rows.shape[1] != self.d or rows.dtype != _ft(self.prec):
+                raise ValueError("append: rows must be %s [count, %d]" % (np.dtype(_ft(self.prec)).name, self.d))
+            src, on_dev = np.ascontiguousarray(rows), 0
+            ptr = src.ctypes.data
+        else:
+            if (not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dim() != 2 or rows.shape[1] != self.d
+                    or rows.dtype != self._torch_ft(self.prec)):
+                raise ValueError("append: rows must be a numpy array or a device tensor [count, %d] of the index's precision" % self.d)
+            src, on_dev = rows.contiguous(), 1
+            torch.cuda.current_stream(src.device).synchronize()  # the copy runs on the null stream
+            ptr = src.data_ptr()
+        count = int(src.shape[0])
+        tg = tptr = None
+        tags_on_dev = 0
+        if tags is not None:
+            if isinstance(tags, np.ndarray):
+                if tags.dtype != np.uint32 or tags.shape != (count,):
+                    raise ValueError("append: tags must be uint32 of length count = %d" % count)
+                tg = np.ascontiguousarray(tags)
+                tptr = tg.ctypes.data
+            else:
+                tg = _words_dev(tags, count, tags.device if isinstance(tags, torch.Tensor) else None, "append: tags")
+                torch.cuda.current_stream(tg.device).synchronize()
+                tptr, tags_on_dev = tg.data_ptr(), 1
+        if self.lib.annhip_index_append(self.h, ptr if count else None, on_dev, count, tptr, tags_on_dev) != 0:
+            raise ValueError("annhip_index_append refused (fixed mode off, a resharded index, narrow rows, too many rows, or "
+                             "tags given without / missing with the index's tags)")
+        return first
+
+    def reserve_tail(self, rows):
+        """annhip_index_reserve_tail: capacity for at least `rows` appended rows, so that later appends do not reallocate.
+        ValueError where the library refuses (as append)."""
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or rows < 0 or \
+                self.lib.annhip_index_reserve_tail(self.h, int(rows)) != 0:
+            raise ValueError("annhip_index_reserve_tail refused rows=%r" % (rows,))
+
+    def drop_tail(self):
+        """annhip_index_drop_tail: forget the appended rows (the capacity is kept); filter and tags are read up to n again."""
+        self.lib.annhip_index_drop_tail(self.h)
+
+    def rows_tensor(self, lo, hi):
+        """annhip_index_copy_rows: a new device tensor [hi - lo, d] holding native rows [lo, hi) of the combined row set
+        (built rows, then the tail).  ValueError for a range outside 0..n_total or a resharded index."""
+        import torch
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.n_total:
+            raise ValueError("rows_tensor: [%d, %d) outside 0..n_total = %d" % (lo, hi, self.n_total))
+        out = torch.empty((hi - lo, self.d), dtype=self._torch_ft(self.prec), device="cuda")
+        torch.cuda.current_stream(out.device).synchronize()
+        if self.lib.annhip_index_copy_rows(self.h, lo, hi, out.data_ptr()) != 0:
+            raise ValueError("annhip_index_copy_rows refused [%d, %d) (a resharded index)" % (lo, hi))
+        return out
+
+    def compact(self, tries=10, rots_before=6, rot_len_before=1, rots_after=1, rot_len_after=1):
+        """Fold the tail into a rebuilt index: Index.precomp over rows_tensor(0, n_total) with this index's k.  Returns a
+        NEW index with n = n_total and no tail; fixed mode, the probe setting, the allow list and the tags (n_total words
+        each) are carried over, ids are unchanged.  The rotations are drawn from libc random(): the caller seeds it.  This
+        index stays as it is; close it when the new one has taken over."""
+        import torch
+        rows = self.rows_tensor(0, self.n_total)
+        new = Index.precomp(rows, self.k, tries, rots_before, rot_len_before, rots_after, rot_len_after)
+        new.set_fixed(bool(self.lib.annhip_index_fixed(self.h)))
+        new.set_probe(min(self.probe, new.d_short))
+        nt = self.n_total
+        if self.filter_count is not None:
+            bits = torch.empty(((nt + 31) // 32,), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            self.lib.annhip_index_copy_words(self.h, 0, bits.data_ptr())
+            if new.lib.annhip_index_set_filter(new.h, bits.data_ptr(), 1) != 0:
+                raise ValueError("compact: the allow list could not be carried over")
+        if self.has_tags:
+            tg = torch.empty((nt,), dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            self.lib.annhip_index_copy_words(self.h, 1, tg.data_ptr())
+            new.set_tags(tg)
+        return new
 
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
     # the names an index of each precision knows: every library serves its own narrow row type (ANNHIP_ROWS_F32 = 2)

@@ -29,6 +29,7 @@
 #include "ann_filter_kernels.h"
 #include "ann_tag_kernels.h"
 #include "ann_kq_kernels.h"
+#include "ann_tail_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -321,7 +322,13 @@ struct annhip_index {
   u32 *filter = NULL;             // annhip_index_set_filter: the index's copy of the allow list, u32[ceil(n / 32)] (NULL = none)
   long long filter_count = -1;    // allowed rows among [0, n), taken when the filter was set (-1 = no filter)
   u32 *tags = NULL;               // annhip_index_set_tags: the index's copy of the rows' tag words, u32[n] (NULL = none)
+  // annhip_index_append: rows added since the build, scanned exactly by every fixed-mode query (ann_tail_kernels.h).
+  // Tail row j has id n + j.  filter and tags are allocated for n + tail_cap rows and hold n + tail_m.
+  FT *d_tail = NULL;              // [tail_cap][d], owned
+  size_t tail_m = 0, tail_cap = 0;
 };
+static size_t n_total(const annhip_index *ix) { return ix->n + ix->tail_m; }
+static size_t filter_words(size_t rows) { return (rows + 31) / 32; }
 
 static QParams make_params(const annhip_index *ix) {
   QParams P;
@@ -458,11 +465,22 @@ extern "C" int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int
     return -1;
   }
   HIPCHECK(hipDeviceSynchronize());
-  if (!ix->tags) ix->tags = dev_alloc<u32>(ix->n);
-  HIPCHECK(hipMemcpy(ix->tags, tags, sizeof(u32) * ix->n, tags_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (!ix->tags) ix->tags = dev_alloc<u32>(ix->n + ix->tail_cap);
+  HIPCHECK(hipMemcpy(ix->tags, tags, sizeof(u32) * n_total(ix), tags_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   return 0;
 }
 extern "C" int annhip_index_has_tags(const annhip_index *ix) { return ix->tags ? 1 : 0; }
+// filter_count := the set bits among rows [0, n_total) of the index's bitmap (synchronous, null stream)
+static void filter_recount(annhip_index *ix) {
+  const size_t rows = n_total(ix);
+  unsigned long long *cnt = dev_alloc<unsigned long long>(1), host = 0;
+  HIPCHECK(hipMemset(cnt, 0, sizeof host));
+  filter_count_kernel<<<grid_for(filter_words(rows), 256, 1024), 256>>>(rows, ix->filter, cnt);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(&host, cnt, sizeof host, hipMemcpyDeviceToHost));
+  HIPCHECK(hipFree(cnt));
+  ix->filter_count = (long long)host;
+}
 // Contract: include/ann_hip.h.  Kernels: ann_filter_kernels.h.
 extern "C" int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, int bits_on_device) {
   if (!bits) {
@@ -478,17 +496,11 @@ extern "C" int annhip_index_set_filter(annhip_index *ix, const uint32_t *bits, i
     fprintf(stderr, "annhip_index_set_filter: the index does not hold rows [0, n) on this device (resharded)\n");
     return -1;
   }
-  const size_t nw = (ix->n + 31) / 32;
+  const size_t nw = filter_words(n_total(ix));
   HIPCHECK(hipDeviceSynchronize());
-  if (!ix->filter) ix->filter = dev_alloc<u32>(nw);
+  if (!ix->filter) ix->filter = dev_alloc<u32>(filter_words(ix->n + ix->tail_cap));
   HIPCHECK(hipMemcpy(ix->filter, bits, sizeof(u32) * nw, bits_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  unsigned long long *cnt = dev_alloc<unsigned long long>(1), host = 0;
-  HIPCHECK(hipMemset(cnt, 0, sizeof host));
-  filter_count_kernel<<<grid_for(nw, 256, 1024), 256>>>(ix->n, ix->filter, cnt);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpy(&host, cnt, sizeof host, hipMemcpyDeviceToHost));
-  HIPCHECK(hipFree(cnt));
-  ix->filter_count = (long long)host;
+  filter_recount(ix);
   return 0;
 }
 extern "C" long long annhip_index_filter_count(const annhip_index *ix) { return ix->filter ? ix->filter_count : -1; }
@@ -542,6 +554,11 @@ extern "C" int annhip_index_set_rows(annhip_index *ix, int rows) {
     return -1;
   }
   if (rows == ANNHIP_ROWS_NARROW) {
+    if (ix->tail_m) {
+      fprintf(stderr, "annhip_index_set_rows: " ANN_NARROW_WHAT " rows and appended rows do not compose (annhip_index_drop_tail, or "
+                      "Index.compact)\n");
+      return -1;
+    }
     if (!(ix->lo == 0 && ix->hi == ix->n)) {
       fprintf(stderr, "annhip_index_set_rows: " ANN_NARROW_WHAT " rows need the whole index on this device (rows [0, n))\n");
       return -1;
@@ -563,6 +580,105 @@ static void drop_half_rows(annhip_index *ix) {
   if (ix->d_points_h) HIPCHECK(hipFree(ix->d_points_h));
   ix->d_points_h = NULL;
   ix->rows = ANNHIP_ROWS_NATIVE;
+}
+
+// ----------------------------------------------------------------------------- appended rows (the tail)
+// Contract: include/ann_hip.h.  Kernels: ann_tail_kernels.h.  All of it synchronous on the null stream.
+static const char *tail_refusal(const annhip_index *ix, size_t count) {
+  return !ix->fixed ? "fixed mode is off (annhip_index_set_fixed); parity-mode queries never see appended rows"
+         : (ix->lo != 0 || ix->hi != ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+         : ix->rows != ANNHIP_ROWS_NATIVE ? "the index reads narrow rows (annhip_index_set_rows); a tail holds native rows only"
+         : (n_total(ix) + count >= 0xFFFFFFF0ull || count >= 0xFFFFFFF0ull) ? "row ids must fit 32 bits"
+                                                                          : NULL;
+}
+// capacity >= rows: the tail buffer and the index's bitmap and tag copies move to larger allocations
+static void tail_grow(annhip_index *ix, size_t rows) {
+  if (rows <= ix->tail_cap) return;
+  HIPCHECK(hipDeviceSynchronize());
+  const size_t cap = std::max(rows, 2 * ix->tail_cap), have = n_total(ix);
+  FT *nt = dev_alloc<FT>(cap * ix->d);
+  if (ix->tail_m) HIPCHECK(hipMemcpy(nt, ix->d_tail, sizeof(FT) * ix->tail_m * ix->d, hipMemcpyDeviceToDevice));
+  if (ix->d_tail) HIPCHECK(hipFree(ix->d_tail));
+  ix->d_tail = nt;
+  if (ix->filter) {
+    u32 *nf = dev_alloc<u32>(filter_words(ix->n + cap));
+    HIPCHECK(hipMemcpy(nf, ix->filter, sizeof(u32) * filter_words(have), hipMemcpyDeviceToDevice));
+    HIPCHECK(hipFree(ix->filter));
+    ix->filter = nf;
+  }
+  if (ix->tags) {
+    u32 *ng = dev_alloc<u32>(ix->n + cap);
+    HIPCHECK(hipMemcpy(ng, ix->tags, sizeof(u32) * have, hipMemcpyDeviceToDevice));
+    HIPCHECK(hipFree(ix->tags));
+    ix->tags = ng;
+  }
+  ix->tail_cap = cap;
+}
+extern "C" int annhip_index_reserve_tail(annhip_index *ix, size_t rows) {
+  if (const char *why = tail_refusal(ix, rows > ix->tail_m ? rows - ix->tail_m : 0)) {
+    fprintf(stderr, "annhip_index_reserve_tail: %s\n", why);
+    return -1;
+  }
+  tail_grow(ix, rows);
+  return 0;
+}
+extern "C" int annhip_index_append(annhip_index *ix, const ftype *rows, int rows_on_device, size_t count, const uint32_t *tags,
+                                   int tags_on_device) {
+  const char *why = tail_refusal(ix, count);
+  if (!why && ix->tags && !tags) why = "the index has tags (annhip_index_set_tags): the new rows need theirs";
+  if (!why && !ix->tags && tags) why = "tags were given but the index has none (annhip_index_set_tags)";
+  if (!why && count && !rows) why = "rows == NULL";
+  if (why) {
+    fprintf(stderr, "annhip_index_append: %s\n", why);
+    return -1;
+  }
+  if (!count) return 0;
+  HIPCHECK(hipDeviceSynchronize());
+  tail_grow(ix, ix->tail_m + count);
+  const size_t at = n_total(ix);
+  HIPCHECK(hipMemcpy(ix->d_tail + ix->tail_m * ix->d, rows, sizeof(FT) * count * ix->d,
+                     rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (ix->tags)
+    HIPCHECK(hipMemcpy(ix->tags + at, tags, sizeof(u32) * count, tags_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  if (ix->filter) {  // the new rows are allowed
+    tail_set_bits_kernel<<<grid_for(filter_words(count) + 1, 256, 1024), 256>>>(ix->filter, at, at + count);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    ix->filter_count += (long long)count;
+  }
+  ix->tail_m += count;
+  return 0;
+}
+extern "C" size_t annhip_index_tail(const annhip_index *ix) { return ix->tail_m; }
+extern "C" int annhip_index_fixed(const annhip_index *ix) { return ix->fixed; }
+// what: 0 = the allow list, ceil(n_total/32) words; 1 = the tags, n_total words -> dst_dev; -1 where the index has none
+extern "C" int annhip_index_copy_words(const annhip_index *ix, int what, uint32_t *dst_dev) {
+  const u32 *src = what == 0 ? ix->filter : what == 1 ? ix->tags : NULL;
+  if (!src) return -1;
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipMemcpy(dst_dev, src, sizeof(u32) * (what == 0 ? filter_words(n_total(ix)) : n_total(ix)), hipMemcpyDeviceToDevice));
+  return 0;
+}
+extern "C" int annhip_index_drop_tail(annhip_index *ix) {
+  if (!ix->tail_m) return 0;
+  HIPCHECK(hipDeviceSynchronize());
+  ix->tail_m = 0;
+  if (ix->filter) filter_recount(ix);  // the bitmap and the tags are read up to n again
+  return 0;
+}
+extern "C" int annhip_index_copy_rows(const annhip_index *ix, size_t lo, size_t hi, ftype *dst_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n || lo > hi || hi > n_total(ix)) {
+    fprintf(stderr, "annhip_index_copy_rows: rows [%zu, %zu) outside 0..n_total = %zu, or a resharded index\n", lo, hi, n_total(ix));
+    return -1;
+  }
+  HIPCHECK(hipDeviceSynchronize());
+  FT *dst = reinterpret_cast<FT *>(dst_dev);
+  const size_t d = ix->d, b_hi = std::min(hi, ix->n);
+  if (lo < b_hi) HIPCHECK(hipMemcpy(dst, ix->d_points + lo * d, sizeof(FT) * (b_hi - lo) * d, hipMemcpyDeviceToDevice));
+  const size_t t_lo = std::max(lo, ix->n);
+  if (t_lo < hi)
+    HIPCHECK(hipMemcpy(dst + (t_lo - lo) * d, ix->d_tail + (t_lo - ix->n) * d, sizeof(FT) * (hi - t_lo) * d, hipMemcpyDeviceToDevice));
+  return 0;
 }
 
 extern "C" annhip_index *annhip_index_create(const save_t *save, const ftype *points, int on_device,
@@ -617,6 +733,7 @@ extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points
   drop_half_rows(ix);  // narrow rows are for the whole index on one device: a resharded index reads native rows
   drop_filter(ix);     // ... and so is the allow list
   drop_tags(ix);       // ... and the rows' tags
+  ix->tail_m = 0;      // ... and the appended rows (the buffer stays)
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -632,6 +749,7 @@ extern "C" void annhip_index_destroy(annhip_index *ix) {
   drop_half_rows(ix);
   drop_filter(ix);
   drop_tags(ix);
+  if (ix->d_tail) HIPCHECK(hipFree(ix->d_tail));
   for (u32 *t : ix->d_tabs)
     if (t) HIPCHECK(hipFree(t));
   for (uint2 *sg : ix->d_segs)
@@ -1406,6 +1524,11 @@ static size_t codes_needed(const annhip_index *ix, size_t Q) {
   return std::min(Q, ((size_t)tries_used * Q + ix->T - 1) / ix->T);
 }
 
+// the exact scan of the appended rows, merged into the rows a fixed-mode call has produced (defined with the exact scan)
+static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const TagQuery *tq, size_t kin,
+                              const size_t *in_ids, const FT *in_d, size_t *ids, FT *dists, unsigned long long *scored,
+                              hipStream_t s);
+
 // ----------------------------------------------------------------------------- query
 // codes_ready: ws.codes already holds the hash codes of this batch (query_gpu computes them chunk by chunk while the
 // batch is still arriving over PCIe)
@@ -1473,6 +1596,9 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
                                      ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter, tq))
       die("fixed mode: stage-2 shape not supported");
     seg_mark(ix, marks, s);
+    if (ix->tail_m)  // appended rows: scanned exactly, merged into the rows just written ("stage2_network" of annhip_stage_ms)
+      launch_tail_merge(ix, Q, y, alias, (size_t)k, tq, (size_t)k, ids_dev, out_d, ids_dev, out_d,
+                        ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
     seg_mark(ix, marks, s);
     seg_mark(ix, marks, s);
     if (marks) ix->seg_used.push_back(marks_store);
@@ -1726,6 +1852,8 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
   launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
   seg_mark(ix, marks, s);
+  if (ix->tail_m)
+    launch_tail_merge(ix, Q, y, alias, kq, tq, kq, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
   seg_mark(ix, marks, s);
   seg_mark(ix, marks, s);
   if (marks) ix->seg_used.push_back(marks_store);
@@ -2226,14 +2354,16 @@ static int exact_check(size_t n, size_t d, size_t k, int self) {
   if (k > n - (self && n ? 1 : 0) || !n) return exact_refuse("k exceeds the number of rows a query can be given");
   return 0;
 }
-// Shape of one annhip_exact_knn call for a kernel that takes up to max_waves waves per workgroup; launch(grid, block,
-// smem, args) starts the scan of one chunk of queries.  prefetch: the kernel moves the next tile through registers.
-template <typename Launch>
-static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
-                     FT *dists_dev, bool generic, int max_waves, bool prefetch, int filtered, Launch &&launch) {
-  // filtered: 0 = every row, 1 = allow list (ann_filter_kernels.h), 2 = tag predicate, with or without an allow list
-  // (ann_tag_kernels.h)
-  // LDS of a workgroup: the row tile, then per wave the selection buffers (and the query + tree scratch of the any-d path)
+// LDS carve-up of one workgroup of the exact scan for a kernel that takes up to max_waves waves: the row tile, then per wave
+// the selection buffers (and the query + tree scratch of the any-d path), then the tile's validity words.  The one source
+// of this arithmetic: exact_run and launch_tail_merge (ann_tail_kernels.h) both size their launches with it.
+// filtered: 0 = every row, 1 = allow list (ann_filter_kernels.h), 2 = tag predicate, with or without an allow list
+// (ann_tag_kernels.h).  prefetch: the kernel moves the next tile through registers.  false: the row does not fit.
+struct ExShape {
+  size_t W, tile_rows, smem, cap;
+  bool prefetch;
+};
+static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool prefetch, int filtered, ExShape &sh) {
   const size_t row_bytes = d * sizeof(FT);
   const size_t cap = k + ANN_EX_SLACK;
   size_t np = ANN_EX_GEN_ELEMS / d;
@@ -2252,9 +2382,19 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
   while (W > 1 && smem_of(W, prefetch) > ANN_EX_LDS_BUDGET) W--;
   if (prefetch && row_bytes > (size_t)ANN_EX_PF * 64 * W * 16) prefetch = false;  // one row is more than the threads hold
   if (prefetch && filtered == 2 && tile_rows_of(W, true) > 64 * W) prefetch = false;  // ... or more tags: one per thread
-  const size_t smem = smem_of(W, prefetch);
-  if (smem > 160 * 1024) return exact_refuse("row too long for the LDS of one CU");
-  const size_t tile_rows = tile_rows_of(W, prefetch);
+  sh.W = W, sh.cap = cap, sh.prefetch = prefetch;
+  sh.smem = smem_of(W, prefetch);
+  sh.tile_rows = tile_rows_of(W, prefetch);
+  return sh.smem <= 160 * 1024;
+}
+// Shape of one annhip_exact_knn call; launch(grid, block, smem, args) starts the scan of one chunk of queries.
+template <typename Launch>
+static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
+                     FT *dists_dev, bool generic, int max_waves, bool prefetch, int filtered, Launch &&launch) {
+  ExShape sh;
+  if (!exact_shape(d, k, generic, max_waves, prefetch, filtered, sh)) return exact_refuse("row too long for the LDS of one CU");
+  const size_t W = sh.W, cap = sh.cap, smem = sh.smem, tile_rows = sh.tile_rows;
+  prefetch = sh.prefetch;
   const size_t qpg = W * ANN_EX_QB;  // queries per workgroup
   // Row ranges: enough workgroups for several rounds over the CUs at small ycnt, one range where the query groups fill
   // the chip already; a range is long enough that its first rows (every one a survivor until k are known) do not count.
@@ -2410,11 +2550,90 @@ extern "C" int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *
   return rc;
 }
 
+// ----------------------------------------------------------------------------- the tail's scan
+// One workgroup per W x ANN_EX_QB queries streams the whole tail (ann_tail_kernels.h).  in_ids / in_d: the rows to merge
+// into, kin entries per query; they may be ids / dists themselves (kin == k).  Runs on s and returns at once.
+static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const TagQuery *tq, size_t kin,
+                              const size_t *in_ids, const FT *in_d, size_t *ids, FT *dists, unsigned long long *scored,
+                              hipStream_t s) {
+  if (!Q || !ix->tail_m) return;
+  const size_t d = ix->d;
+  const int filtered = tq ? 2 : ix->filter ? 1 : 0;
+  TailArgs A;
+  A.tail = ix->d_tail, A.y = y, A.in_ids = in_ids, A.in_d = in_d, A.out_ids = ids, A.out_d = dists;
+  A.bits = ix->filter, A.tags = tq ? tq->tags : NULL, A.qmask = tq ? tq->qmask : NULL, A.qvalue = tq ? tq->qvalue : NULL;
+  A.scored = scored;
+  A.n = (u32)ix->n, A.m = (u32)ix->tail_m, A.Q = (u32)Q;
+  A.d = (int)d, A.k = (int)k, A.kin = (int)kin, A.self = alias ? 1 : 0;
+  auto shape = [&](bool generic, int max_waves, bool prefetch) {
+    ExShape sh;
+    if (!exact_shape(d, k, generic, max_waves, prefetch, filtered, sh)) die("launch_tail_merge: row too long for the LDS of one CU");
+    A.tile_rows = (int)sh.tile_rows, A.cap = (int)sh.cap, A.prefetch = sh.prefetch ? 1 : 0;
+    return sh;
+  };
+  const int code = layout_code(d);
+  if (layout_is_generic(code)) {
+    const ExShape sh = shape(true, ANN_EX_GEN_WAVES, false);
+    allow_lds(tail_merge_generic_kernel, sh.smem);
+    hipLaunchKernelGGL(tail_merge_generic_kernel, dim3((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))),
+                       dim3((unsigned)(64 * sh.W)), sh.smem, s, A);
+  } else {
+    with_value(QueryLayouts{}, code, [&](auto dc) {
+      constexpr int D = decltype(dc)::value;
+      if constexpr (D != 0 && !OcCode<D>::GEN) {
+        const ExShape sh = shape(false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH);
+        const dim3 grid((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))), block((unsigned)(64 * sh.W));
+        auto go = [&](auto kernel) {
+          allow_lds(kernel, sh.smem);
+          hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, A);
+        };
+        if (filtered == 2) go(tail_merge_kernel<D, TAIL_TAGS>);
+        else if (filtered == 1) go(tail_merge_kernel<D, TAIL_BITS>);
+        else go(tail_merge_kernel<D, TAIL_ALL>);
+      }
+    });
+  }
+  HIPCHECK(hipGetLastError());
+}
+
+// The three exact scans of an index: over the built rows as before, then -- where rows have been appended -- the tail's
+// scan merged in.  kq = the k of the call.  qmask_dev == NULL: untagged.
+static int index_exact(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq, const uint32_t *qmask_dev,
+                       const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  if (qmask_dev && !ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
+  const ftype *pts = reinterpret_cast<const ftype *>(ix->d_points);
+  auto built = [&](size_t k, size_t *ids, ftype *dists) {
+    if (!qmask_dev) return annhip_exact_knn_filtered(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->filter, ids, dists);
+    return annhip_exact_knn_tagged(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->tags, ix->filter, qmask_dev, qvalue_dev, ids, dists);
+  };
+  if (!ix->tail_m) return built(kq, ids_dev, dists_dev);
+  if (const int rc = exact_check(n_total(ix), ix->d, kq, alias)) return rc;
+  if (!ycnt) return 0;
+  const size_t kin = std::min(kq, ix->n - (alias && ix->n ? 1 : 0));  // what the built rows can fill
+  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  const FT *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  int rc = 0;
+  if (kin == kq) {
+    if ((rc = built(kq, ids_dev, dists_dev))) return rc;
+    launch_tail_merge(ix, ycnt, y, alias, kq, qmask_dev ? &tq : NULL, kq, ids_dev, dd, ids_dev, dd, NULL, 0);
+  } else {  // fewer built rows than kq: their scan goes to a buffer of its own
+    size_t *ti = kin ? dev_alloc<size_t>(ycnt * kin) : NULL;
+    FT *td = kin ? dev_alloc<FT>(ycnt * kin) : NULL;
+    if (kin) rc = built(kin, ti, reinterpret_cast<ftype *>(td));
+    if (!rc) launch_tail_merge(ix, ycnt, y, alias, kq, qmask_dev ? &tq : NULL, kin, ti, td, ids_dev, dd, NULL, 0);
+    HIPCHECK(hipStreamSynchronize(0));
+    if (ti) HIPCHECK(hipFree(ti));
+    if (td) HIPCHECK(hipFree(td));
+  }
+  HIPCHECK(hipStreamSynchronize(0));
+  return rc;
+}
+
 extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t *ids_dev,
                                         ftype *dists_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  return annhip_exact_knn_filtered(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
-                                   ix->filter, ids_dev, dists_dev);
+  return index_exact(ix, ycnt, y_dev, alias, ix->k, NULL, NULL, ids_dev, dists_dev);
 }
 
 extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
@@ -2422,8 +2641,8 @@ extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, co
                                                ftype *dists_dev) {
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
-  return annhip_exact_knn_tagged(ix->n, ix->d, ix->k, reinterpret_cast<const ftype *>(ix->d_points), ycnt, y_dev, alias,
-                                 ix->tags, ix->filter, qmask_dev, qvalue_dev, ids_dev, dists_dev);
+  if (!qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
+  return index_exact(ix, ycnt, y_dev, alias, ix->k, qmask_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
 // Contract: include/ann_hip.h.  The three exact scans with a k of the call's own; their refusals.
@@ -2432,11 +2651,7 @@ extern "C" int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const f
                                           ftype *dists_dev) {
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
-  const ftype *pts = reinterpret_cast<const ftype *>(ix->d_points);
-  if (!qmask_dev) return annhip_exact_knn_filtered(ix->n, ix->d, kq, pts, ycnt, y_dev, alias, ix->filter, ids_dev, dists_dev);
-  if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
-  return annhip_exact_knn_tagged(ix->n, ix->d, kq, pts, ycnt, y_dev, alias, ix->tags, ix->filter, qmask_dev, qvalue_dev, ids_dev,
-                                 dists_dev);
+  return index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
 // ----------------------------------------------------------------------------- precomp

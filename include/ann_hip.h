@@ -130,6 +130,54 @@ int annhip_filter_pack(size_t n, const uint8_t *flags_dev, uint32_t *bits_dev, v
  * (annhip_query_tagged is declared below, beside annhip_query_on, where the workspace type is known.) */
 int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int tags_on_device);
 int annhip_index_has_tags(const annhip_index *ix);
+/* Appended rows of fixed mode: the tail (default: none).  A built index is frozen; annhip_index_append adds rows to it
+ * without a rebuild.  Throughout, n = the rows the index was built from (what annhip_index_info keeps reporting), m = the
+ * current tail length, n_total = n + m; tail row j has id n + j.  The rows go into a flat buffer the index owns, and every
+ * fixed-mode query scans ALL of it exactly and merges the result into the index's answer (ann_tail_kernels.h): appended
+ * rows have no bucket entries and no graph edges and need neither.  The cost of a step grows with ycnt * m; rebuild over
+ * all n_total rows (Index.compact in the Python package) when the tail has grown.
+ * annhip_index_append: the index copies `count` rows of d values (native ftype; rows_on_device: device or host pointer)
+ * into its tail buffer, 16-byte aligned like the point rows; capacity doubles on growth; annhip_index_destroy frees it.
+ * Synchronous, on the null stream, as annhip_index_set_filter is; the caller must not append while batches on this index are
+ * in flight (growth moves the buffer).  Returns 0; count == 0 returns 0 and does nothing.  Refused -- -1, one line on stderr,
+ * nothing changed -- while fixed mode is off; on a resharded index; while annhip_index_rows() != ANNHIP_ROWS_NATIVE; when
+ * n_total + count >= 0xFFFFFFF0; when the index has tags and tags == NULL; when tags != NULL and the index has no tags.
+ * With an allow list set the new rows are allowed: the index extends its bitmap with one-bits and adds count to
+ * annhip_index_filter_count.  With tags set the index appends the `count` tag words (tags_on_device as above).
+ * annhip_index_reserve_tail: capacity >= rows, so that later appends do not reallocate; 0, or -1 for the refusals above.
+ * annhip_index_tail: m.
+ * annhip_index_copy_rows: native rows [lo, hi) of the combined row set (built rows, then tail) -> dst_dev (device);
+ * synchronous; -1 when the range is outside 0..n_total or the index is resharded.
+ * annhip_index_drop_tail: m = 0, the bitmap and tag copies are read up to n again; the capacity is kept.  Always returns 0.
+ * With m == 0 every entry point launches exactly what it launched before this feature and returns the same bits.
+ * With m > 0:
+ *   Fixed-mode queries -- annhip_query, annhip_query_on and annhip_stream_* while fixed mode is on, annhip_query_tagged and
+ *   annhip_query_k: let R(q) be the result row as computed without the tail, its pads (entries with id >= n) dropped.  The
+ *   call returns the k (or kq) smallest (distance, id) keys among R(q) and {(dist(q, n+j), n+j) : tail row j valid for
+ *   q}, ascending, padded with (n_total, +inf).  dist is the query path's squared L2 bit for bit (the contract of
+ *   annhip_exact_knn).  A tail row is valid under the rules of any row id: allowed by the allow list when one is set;
+ *   passing the query's tag test in a tagged call; not row q when the call is aliased (query q leaves out row id q,
+ *   wherever it lives).  The tail does not depend on the probe setting.  The merge runs on the call's stream.
+ *   annhip_index_set_filter expects ceil(n_total/32) words and annhip_index_set_tags n_total words: one array serves both
+ *   halves (the index's kernels only ever test ids < n).  annhip_index_filter_count counts rows among [0, n_total).
+ *   annhip_index_exact_query, _tagged and _k return the exact neighbours over all n_total rows under the same validity
+ *   rules; k > n_total - alias is refused where k > n - alias was.
+ *   annhip_index_set_rows with a narrow type is refused (-1): narrow rows and a tail do not compose.
+ *   annhip_index_reshard drops the tail.  annhip_index_set_fixed(ix, 0) keeps it stored.
+ *   NOT covered -- these never see the tail: parity-mode queries, annhip_sh_*, annhip_query_slice, query_gpu,
+ *   annhip_index_export, annhip_index_checksum and index files (annhip_save_write).
+ * annhip_stats out[3] additionally counts, while profile = 1, the (query, valid tail row) pairs the tail's scan scored. */
+int annhip_index_append(annhip_index *ix, const ftype *rows, int rows_on_device, size_t count, const uint32_t *tags,
+                        int tags_on_device);
+int annhip_index_reserve_tail(annhip_index *ix, size_t rows);
+size_t annhip_index_tail(const annhip_index *ix);
+int annhip_index_copy_rows(const annhip_index *ix, size_t lo, size_t hi, ftype *dst_dev);
+int annhip_index_drop_tail(annhip_index *ix);
+/* What Index.compact carries over to the rebuilt index.  annhip_index_fixed: 0 or 1 (annhip_index_set_fixed).
+ * annhip_index_copy_words: the index's own copy of the allow list (what = 0: ceil(n_total/32) words) or of the tags (what =
+ * 1: n_total words) -> dst_dev (device), synchronous; -1 where the index has none, or for another `what`. */
+int annhip_index_fixed(const annhip_index *ix);
+int annhip_index_copy_words(const annhip_index *ix, int what, uint32_t *dst_dev);
 /* Opt-in binary16 point rows (default ANNHIP_ROWS_NATIVE = the reference's results, bit for bit).  With ANNHIP_ROWS_F16,
  * annhip_query / annhip_query_on / annhip_query_slice / annhip_stream_* on this index return exactly what the reference
  * returns for query(save, h(P), y), where h(P) is the point matrix rounded to IEEE binary16 (round to nearest even;
@@ -475,7 +523,8 @@ void annhip_profile(annhip_index *ix, int profile);
  * after reading). */
 void annhip_stats(annhip_index *ix, double out[8], int reset);
 /* While profiling, annhip_query also drops HIP events at its stage boundaries; out[0..5] = accumulated ms of
- * hash codes, stage-1 kernel, finalize + exact fallback, stage-2 rows, stage-2 network, id widening. */
+ * hash codes, stage-1 kernel, finalize + exact fallback, stage-2 rows, stage-2 network, id widening.  Fixed mode has no
+ * stage-2 network: there out[4] is the scan of the appended rows (annhip_index_append), 0 while the tail is empty. */
 void annhip_stage_ms(annhip_index *ix, double out[6]);
 /* The same through the host-pointer ABI: annhip_host_profile(1) makes the indexes resident behind query_gpu() /
  * precomp_gpu() record their stage-1 launches; annhip_host_stats() = annhip_stats() of the index resident for `save`

@@ -19,10 +19,15 @@ pytestmark = pytest.mark.gpu
 
 NP = {"f32": np.float32, "f64": np.float64}
 # a row length for every code annhip_layout_code(d) returns (the lists of tests/test_gpu_rows_f16.py::LAYOUTS and
-# tests/test_layout_table.py::F64), plus 100 and 131
-D_F32 = [128, 80, 96, 160, 192, 320, 384, 24, 48, 28, 280, 112, 224, 100, 70, 50, 36, 150, 30, 260, 300, 2084, 131]
+# tests/test_layout_table.py::F64), plus 100 and 131; 40 in f32 is code -82 (5 lanes x 2 chunks), which those lists lack
+D_F32 = [128, 80, 96, 160, 192, 320, 384, 24, 48, 28, 280, 112, 224, 100, 70, 50, 36, 150, 30, 260, 300, 2084, 131, 40]
 D_F64 = [128, 512, 1024, 40, 80, 48, 96, 160, 192, 12, 24, 20, 14, 28, 56, 112, 100, 36, 33, 150, 300, 2084, 131]
 LAYOUT_CASES = [("f32", d) for d in D_F32] + [("f64", d) for d in D_F64]
+# the lists above plus every power of two the layout table holds (RowLay<D>): the row lengths the filtered and tagged
+# scans, the fixed-mode query families and the tail are swept over.  tests/test_layout_table.py proves that no row
+# length in 1..4096 has a code that SWEEP lacks.
+SWEEP = {"f32": D_F32 + [16, 32, 64, 256, 512, 1024], "f64": D_F64 + [16, 32, 64, 256]}
+SWEEP_CASES = [(p, d) for p in ("f32", "f64") for d in SWEEP[p]]
 
 
 def np_tree(m):

@@ -28,6 +28,23 @@ def _build(prec, n, d, k, T, seed):
     return orc, pts, tp, ix
 
 
+def pts_bytes(prec):
+    return 4 if prec == "f32" else 8
+
+
+def _build_host(prec, n, d, k, T, seed):
+    """_build with the tables and the graph from the oracle's precomp on the host (the device's are bit-identical to them):
+    for rows of more than 4096 bytes, which the device precomp's hashing kernel has no room for."""
+    orc = O.CpuBackend(prec, "oracle")
+    O.srandom(seed)
+    orc.rand_norm_reset()
+    pts = np.ascontiguousarray(orc.gen_rand(n * d).reshape(n, d))
+    tp = torch.from_numpy(pts).cuda()
+    O.srandom(seed + 1)
+    ix = A.Index.from_save(A.Save.from_dict(prec, orc.precomp(pts, k, T)[2]), tp)
+    return orc, pts, tp, ix
+
+
 def _codes_of(eng, ty, T):
     codes = torch.empty((ty.shape[0], T), dtype=torch.int32, device="cuda")
     with eng.use(None):
@@ -119,14 +136,21 @@ def test_zero_pair_bits_is_todays_fixed_mode(prec):
         ix.close()
 
 
-@pytest.mark.parametrize("prec", ["f32", "f64"])
-@pytest.mark.parametrize("d", [32, 80, 33, 100, 300])  # 100: a folded layout; 300: the any-d hash kernel
+# 100: a folded layout; 300: the any-d hash kernel.  MORE: with the five above, a row length for every layout code of the
+# precision (tests/test_layout_table.py checks that none is missing); these run 64 queries, the first five 200.
+RANKING_D = [32, 80, 33, 100, 300]
+RANKING_MORE = {"f32": [16, 64, 128, 256, 512, 1024, 96, 160, 192, 320, 384, 24, 48, 28, 280, 112, 224, 50, 150, 260, 2084, 40],
+                "f64": [16, 64, 128, 256, 512, 40, 48, 96, 160, 192, 12, 24, 20, 14, 28, 56, 112, 36, 150, 2084]}
+RANKING_CASES = [(p, d) for d in RANKING_D for p in ("f32", "f64")] + [(p, d) for p in ("f32", "f64") for d in RANKING_MORE[p]]
+
+
+@pytest.mark.parametrize("prec,d", RANKING_CASES, ids=["%d-%s" % (d, p) for p, d in RANKING_CASES])
 def test_ranking_is_the_smallest_projection_magnitudes(prec, d):
     """codes = the hash kernels' codes; bits = the b smallest |projection|, ascending, against float64 projections: two
     magnitudes may swap (or swap across the b-th place) only when they differ by less than the rounding bound of a
     length-d dot product, d * eps * |y - means| * |base| -- an absolute bound (the smallest magnitudes are ~1e-5 of the terms)."""
-    T, Q = 4, 200
-    orc, pts, tp, ix = _build(prec, 3000, d, 5, T, 5200 + d)
+    T, Q = 4, 200 if d in RANKING_D else 64
+    orc, pts, tp, ix = (_build_host if d * pts_bytes(prec) > 4096 else _build)(prec, 3000, d, 5, T, 5200 + d)
     try:
         y = np.ascontiguousarray(orc.gen_rand(Q * d).reshape(Q, d))
         ty = torch.from_numpy(y).cuda()

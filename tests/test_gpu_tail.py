@@ -19,9 +19,10 @@ from tests.test_gpu_query_k import _np, _same_bits, _tenants
 
 pytestmark = pytest.mark.gpu
 
-# power of two, static lane groups, folded, any-d, kg >= 32 (one shape per kernel family)
+# power of two, static lane groups, folded, any-d, kg >= 32 (one shape per kernel family); then a generic layout
+# (tail_merge_generic_kernel) and one with 8 chunks per lane (8 waves, no prefetch: the ex_fill_tile branch of the tile loop)
 SHAPES = [("f32", 5000, 64, 10, 6), ("f64", 2500, 80, 8, 3), ("f32", 3000, 100, 10, 3), ("f32", 2000, 33, 6, 2),
-          ("f64", 2000, 16, 33, 2)]
+          ("f64", 2000, 16, 33, 2), ("f64", 1500, 300, 5, 2), ("f32", 2000, 384, 6, 2)]
 Q = 37  # the last query group of a wave (4 queries) and of a workgroup is ragged
 
 
@@ -199,12 +200,13 @@ def test_exact_query_covers_the_tail(prec, n, d, kg, T):
         ix.close(), twin.close()
 
 
-def test_exact_query_k_beyond_the_built_rows():
+@pytest.mark.parametrize("prec,d", [("f32", 32), ("f64", 300)])  # 300: the generic kernel's seeding with fewer than k rows
+def test_exact_query_k_beyond_the_built_rows(prec, d):
     """k > n - alias was refused; with a tail the limit is n_total - alias, and the built rows fill only part of a row."""
-    n, d, m = 40, 32, 30
-    pts, tp, ix, twin = _twins("f32", n, d, 5, 1, 9250)
+    n, m = 40, 30
+    pts, tp, ix, twin = _twins(prec, n, d, 5, 1, 9250)
     try:
-        ttail = torch.from_numpy(_rows("f32", m, d, 99)).cuda()
+        ttail = torch.from_numpy(_rows(prec, m, d, 99)).cuda()
         ix.append(ttail)
         both = torch.cat([tp, ttail]).contiguous()
         ta = both[:16].contiguous()

@@ -3,6 +3,8 @@ looked up through the layout table of approximatenn_amd/csrc/ann_host.hip), pinn
 import pytest
 
 from approximatenn_amd import _lib
+from tests.test_gpu_exact_knn import SWEEP
+from tests.test_gpu_probe import RANKING_D, RANKING_MORE
 from tests.test_gpu_rows_f16 import LAYOUTS
 
 UNALIGNED, FOLD2, FOLD3, FOLD4, FOLD4G, FOLD5G = -241, -243, -244, -245, -246, -247  # ANN_D_* (ann_device.h)
@@ -29,6 +31,24 @@ def test_f32_codes_of_the_f16_row_layouts():
 
 def test_f64_codes():
     assert _codes("f64", F64) == F64
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_the_sweep_list_has_a_row_length_for_every_code(prec):
+    """tests/test_gpu_exact_knn.py::SWEEP is the case list of the per-layout GPU sweeps: every code that any row length
+    dispatches to must have a row length in it."""
+    every = set(_codes(prec, range(1, 4097)).values())
+    swept = set(_codes(prec, SWEEP[prec]).values())
+    assert every == swept, "codes without a row length in SWEEP[%s]: %s" % (prec, sorted(every - swept))
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_the_probe_ranking_list_has_one_row_length_for_every_code(prec):
+    """tests/test_gpu_probe.py::test_ranking_is_the_smallest_projection_magnitudes runs RANKING_D + RANKING_MORE[prec]."""
+    ds = RANKING_D + RANKING_MORE[prec]
+    codes = _codes(prec, ds)
+    assert set(codes.values()) == set(_codes(prec, range(1, 4097)).values())
+    assert len(set(codes.values())) == len(ds), "two row lengths of one code: %s" % sorted(codes.items())
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])

@@ -91,6 +91,10 @@ def load(prec="f32"):
     lib.annhip_index_reserve_tail.argtypes = [vp, sz]
     lib.annhip_index_tail.restype = sz
     lib.annhip_index_tail.argtypes = [vp]
+    lib.annhip_index_hash_tail.restype = C.c_int
+    lib.annhip_index_hash_tail.argtypes = [vp]
+    lib.annhip_index_tail_hashed.restype = sz
+    lib.annhip_index_tail_hashed.argtypes = [vp]
     lib.annhip_index_copy_rows.restype = C.c_int
     lib.annhip_index_copy_rows.argtypes = [vp, sz, sz, vp]
     lib.annhip_index_drop_tail.restype = C.c_int
@@ -220,6 +224,7 @@ EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp
             "annhip_index_exact_query_tagged",
             "annhip_query_k", "annhip_index_max_query_k", "annhip_index_exact_query_k",
             "annhip_index_append", "annhip_index_reserve_tail", "annhip_index_tail", "annhip_index_copy_rows", "annhip_index_drop_tail",
+            "annhip_index_hash_tail", "annhip_index_tail_hashed",
             "annhip_index_fixed", "annhip_index_copy_words",
             "annhip_index_export", "annhip_index_reshard", "annhip_save_write", "annhip_save_read", "annhip_precomp_index", "annhip_precomp_begin", "annhip_precomp_info", "annhip_precomp_init_merged", "annhip_precomp_hash",
             "annhip_precomp_try", "annhip_precomp_merge", "annhip_precomp_graph", "annhip_precomp_finish", "annhip_query", "annhip_workspace_create", "annhip_workspace_destroy", "annhip_query_on", "annhip_query_slice", "annhip_stream_open", "annhip_stream_submit", "annhip_stream_collect", "annhip_stream_close",

@@ -562,6 +562,19 @@ class Index:
         """annhip_index_drop_tail: forget the appended rows (the capacity is kept); filter and tags are read up to n again."""
         self.lib.annhip_index_drop_tail(self.h)
 
+    def hash_tail(self):
+        """annhip_index_hash_tail: file all current tail rows under their hash codes, so that a fixed-mode query fetches only
+        the tail rows of the buckets it probes instead of scanning them all.  Those rows are then found approximately, like
+        built rows; rows appended later are scanned exactly until the next call.  ValueError where the library refuses
+        (fixed mode off, a resharded index); nothing changes then.  Do not call it while batches are in flight."""
+        if self.lib.annhip_index_hash_tail(self.h) != 0:
+            raise ValueError("annhip_index_hash_tail refused (fixed mode off, or a resharded index)")
+
+    @property
+    def tail_hashed(self):
+        """annhip_index_tail_hashed: mh, the tail rows [0, mh) that queries look up by hash code."""
+        return int(self.lib.annhip_index_tail_hashed(self.h))
+
     def rows_tensor(self, lo, hi):
         """annhip_index_copy_rows: a new device tensor [hi - lo, d] holding native rows [lo, hi) of the combined row set
         (built rows, then the tail).  ValueError for a range outside 0..n_total or a resharded index."""

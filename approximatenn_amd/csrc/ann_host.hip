@@ -30,6 +30,7 @@
 #include "ann_tag_kernels.h"
 #include "ann_kq_kernels.h"
 #include "ann_tail_kernels.h"
+#include "ann_tail_hash_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -326,6 +327,12 @@ struct annhip_index {
   // Tail row j has id n + j.  filter and tags are allocated for n + tail_cap rows and hold n + tail_m.
   FT *d_tail = NULL;              // [tail_cap][d], owned
   size_t tail_m = 0, tail_cap = 0;
+  // annhip_index_hash_tail: tail rows [0, tail_mh) are looked up by hash code (ann_tail_hash_kernels.h), [tail_mh, tail_m)
+  // are scanned exactly.  The structure names rows by j, not by address: it survives a move of d_tail.
+  size_t tail_mh = 0;
+  u32 *tail_codes = NULL;  // [tail_mh][T]
+  u32 *tail_off = NULL;    // [T][2^ds + 1], offsets into tail_rows (they include t * tail_mh)
+  u32 *tail_rows = NULL;   // [T][tail_mh]
 };
 static size_t n_total(const annhip_index *ix) { return ix->n + ix->tail_m; }
 static size_t filter_words(size_t rows) { return (rows + 31) / 32; }
@@ -591,6 +598,14 @@ static const char *tail_refusal(const annhip_index *ix, size_t count) {
          : (n_total(ix) + count >= 0xFFFFFFF0ull || count >= 0xFFFFFFF0ull) ? "row ids must fit 32 bits"
                                                                           : NULL;
 }
+// mh = 0: the codes and the CSR of the hashed tail rows are freed (the caller has synchronised)
+static void drop_tail_hash(annhip_index *ix) {
+  for (u32 **p : {&ix->tail_codes, &ix->tail_off, &ix->tail_rows}) {
+    if (*p) HIPCHECK(hipFree(*p));
+    *p = NULL;
+  }
+  ix->tail_mh = 0;
+}
 // capacity >= rows: the tail buffer and the index's bitmap and tag copies move to larger allocations
 static void tail_grow(annhip_index *ix, size_t rows) {
   if (rows <= ix->tail_cap) return;
@@ -650,6 +665,7 @@ extern "C" int annhip_index_append(annhip_index *ix, const ftype *rows, int rows
   return 0;
 }
 extern "C" size_t annhip_index_tail(const annhip_index *ix) { return ix->tail_m; }
+extern "C" size_t annhip_index_tail_hashed(const annhip_index *ix) { return ix->tail_mh; }
 extern "C" int annhip_index_fixed(const annhip_index *ix) { return ix->fixed; }
 // what: 0 = the allow list, ceil(n_total/32) words; 1 = the tags, n_total words -> dst_dev; -1 where the index has none
 extern "C" int annhip_index_copy_words(const annhip_index *ix, int what, uint32_t *dst_dev) {
@@ -663,6 +679,7 @@ extern "C" int annhip_index_drop_tail(annhip_index *ix) {
   if (!ix->tail_m) return 0;
   HIPCHECK(hipDeviceSynchronize());
   ix->tail_m = 0;
+  drop_tail_hash(ix);
   if (ix->filter) filter_recount(ix);  // the bitmap and the tags are read up to n again
   return 0;
 }
@@ -734,6 +751,7 @@ extern "C" void annhip_index_reshard(annhip_index *ix, const ftype *shard_points
   drop_filter(ix);     // ... and so is the allow list
   drop_tags(ix);       // ... and the rows' tags
   ix->tail_m = 0;      // ... and the appended rows (the buffer stays)
+  drop_tail_hash(ix);
   if (ix->own_points && ix->d_points) HIPCHECK(hipFree(ix->d_points));
   ix->own_points = false;
   ix->d_points = const_cast<FT *>(reinterpret_cast<const FT *>(shard_points_dev));
@@ -750,6 +768,7 @@ extern "C" void annhip_index_destroy(annhip_index *ix) {
   drop_filter(ix);
   drop_tags(ix);
   if (ix->d_tail) HIPCHECK(hipFree(ix->d_tail));
+  drop_tail_hash(ix);
   for (u32 *t : ix->d_tabs)
     if (t) HIPCHECK(hipFree(t));
   for (uint2 *sg : ix->d_segs)
@@ -1527,7 +1546,11 @@ static size_t codes_needed(const annhip_index *ix, size_t Q) {
 // the exact scan of the appended rows, merged into the rows a fixed-mode call has produced (defined with the exact scan)
 static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const TagQuery *tq, size_t kin,
                               const size_t *in_ids, const FT *in_d, size_t *ids, FT *dists, unsigned long long *scored,
-                              hipStream_t s);
+                              hipStream_t s, size_t skip = 0);
+// the hashed tail rows of the buckets the call probes, merged in place into the rows it has produced (likewise)
+static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size_t k, const TagQuery *tq, const u32 *codes,
+                                   const unsigned char *pbits, int pb, size_t *ids, FT *dists, unsigned long long *scored,
+                                   hipStream_t s);
 
 // ----------------------------------------------------------------------------- query
 // codes_ready: ws.codes already holds the hash codes of this batch (query_gpu computes them chunk by chunk while the
@@ -1596,9 +1619,14 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
                                      ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter, tq))
       die("fixed mode: stage-2 shape not supported");
     seg_mark(ix, marks, s);
-    if (ix->tail_m)  // appended rows: scanned exactly, merged into the rows just written ("stage2_network" of annhip_stage_ms)
+    // appended rows, merged into the rows just written ("stage2_network" of annhip_stage_ms): the hashed ones through the
+    // buckets this call probes, the rest scanned exactly
+    if (ix->tail_mh)
+      launch_tail_hash_merge(ix, Q, y, (size_t)k, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
+                             ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+    if (ix->tail_m > ix->tail_mh)
       launch_tail_merge(ix, Q, y, alias, (size_t)k, tq, (size_t)k, ids_dev, out_d, ids_dev, out_d,
-                        ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+                        ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->tail_mh);
     seg_mark(ix, marks, s);
     seg_mark(ix, marks, s);
     if (marks) ix->seg_used.push_back(marks_store);
@@ -1852,8 +1880,12 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
   launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
   seg_mark(ix, marks, s);
-  if (ix->tail_m)
-    launch_tail_merge(ix, Q, y, alias, kq, tq, kq, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+  if (ix->tail_mh)
+    launch_tail_hash_merge(ix, Q, y, kq, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
+                           ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+  if (ix->tail_m > ix->tail_mh)
+    launch_tail_merge(ix, Q, y, alias, kq, tq, kq, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s,
+                      ix->tail_mh);
   seg_mark(ix, marks, s);
   seg_mark(ix, marks, s);
   if (marks) ix->seg_used.push_back(marks_store);
@@ -2553,17 +2585,18 @@ extern "C" int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *
 // ----------------------------------------------------------------------------- the tail's scan
 // One workgroup per W x ANN_EX_QB queries streams the whole tail (ann_tail_kernels.h).  in_ids / in_d: the rows to merge
 // into, kin entries per query; they may be ids / dists themselves (kin == k).  Runs on s and returns at once.
+// skip: tail rows [0, skip) are already in the rows to merge into (the hashed tier); ids below n + skip count as real there.
 static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const TagQuery *tq, size_t kin,
                               const size_t *in_ids, const FT *in_d, size_t *ids, FT *dists, unsigned long long *scored,
-                              hipStream_t s) {
-  if (!Q || !ix->tail_m) return;
+                              hipStream_t s, size_t skip) {
+  if (!Q || ix->tail_m <= skip) return;
   const size_t d = ix->d;
   const int filtered = tq ? 2 : ix->filter ? 1 : 0;
   TailArgs A;
-  A.tail = ix->d_tail, A.y = y, A.in_ids = in_ids, A.in_d = in_d, A.out_ids = ids, A.out_d = dists;
+  A.tail = ix->d_tail + skip * d, A.y = y, A.in_ids = in_ids, A.in_d = in_d, A.out_ids = ids, A.out_d = dists;
   A.bits = ix->filter, A.tags = tq ? tq->tags : NULL, A.qmask = tq ? tq->qmask : NULL, A.qvalue = tq ? tq->qvalue : NULL;
   A.scored = scored;
-  A.n = (u32)ix->n, A.m = (u32)ix->tail_m, A.Q = (u32)Q;
+  A.n = (u32)(ix->n + skip), A.m = (u32)(ix->tail_m - skip), A.Q = (u32)Q;
   A.d = (int)d, A.k = (int)k, A.kin = (int)kin, A.self = alias ? 1 : 0;
   auto shape = [&](bool generic, int max_waves, bool prefetch) {
     ExShape sh;
@@ -2594,6 +2627,94 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
     });
   }
   HIPCHECK(hipGetLastError());
+}
+
+// ----------------------------------------------------------------------------- the hashed tail
+// One wave per query (ann_tail_hash_kernels.h).  LDS per wave: one selection buffer of exact_shape()'s cap plus k keys,
+// the any-d form's query and tree scratch, the candidate chunk; the waves come down until the workgroup fits.
+static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size_t k, const TagQuery *tq, const u32 *codes,
+                                   const unsigned char *pbits, int pb, size_t *ids, FT *dists, unsigned long long *scored,
+                                   hipStream_t s) {
+  if (!Q || !ix->tail_mh) return;
+  const size_t d = ix->d;
+  const int filtered = tq ? 2 : ix->filter ? 1 : 0;
+  TailHashArgs A;
+  A.t.tail = ix->d_tail, A.t.y = y, A.t.in_ids = ids, A.t.in_d = dists, A.t.out_ids = ids, A.t.out_d = dists;
+  A.t.bits = ix->filter, A.t.tags = tq ? tq->tags : NULL, A.t.qmask = tq ? tq->qmask : NULL, A.t.qvalue = tq ? tq->qvalue : NULL;
+  A.t.scored = scored;
+  A.t.n = (u32)ix->n, A.t.m = (u32)ix->tail_m, A.t.Q = (u32)Q;
+  A.t.d = (int)d, A.t.k = (int)k, A.t.kin = (int)k, A.t.self = 0, A.t.tile_rows = 0, A.t.prefetch = 0;
+  A.codes = codes, A.pbits = pbits, A.pb = pbits ? pb : 0;
+  A.tcodes = ix->tail_codes, A.off = ix->tail_off, A.rows = ix->tail_rows, A.mh = (u32)ix->tail_mh, A.T = ix->T, A.ds = (int)ix->ds;
+  struct Shape {
+    size_t W, smem;
+  };
+  auto shape = [&](bool generic, int max_waves) {
+    ExShape sh;
+    if (!exact_shape(d, k, generic, max_waves, false, filtered, sh)) die("launch_tail_hash_merge: row too long for the LDS of one CU");
+    A.t.cap = (int)sh.cap;
+    size_t np = ANN_EX_GEN_ELEMS / d;
+    np = np < 1 ? 1 : (np > ANN_WAVE ? ANN_WAVE : np);
+    const size_t wave_bytes = sizeof(Key) * (sh.cap + k) + (generic ? (((1 + np) * d * sizeof(FT) + 15) & ~(size_t)15) : 0) +
+                              sizeof(u32) * thash_wave_words(ix->T);
+    Shape r{(size_t)max_waves, 0};
+    while (r.W > 1 && r.W * wave_bytes > ANN_EX_LDS_BUDGET) r.W--;
+    r.smem = r.W * wave_bytes;
+    if (r.smem > 160 * 1024) die("launch_tail_hash_merge: row too long for the LDS of one CU");
+    return r;
+  };
+  const int code = layout_code(d);
+  if (layout_is_generic(code)) {
+    const Shape sh = shape(true, ANN_EX_GEN_WAVES);
+    allow_lds(tail_hash_merge_generic_kernel, sh.smem);
+    hipLaunchKernelGGL(tail_hash_merge_generic_kernel, dim3((unsigned)((Q + sh.W - 1) / sh.W)), dim3((unsigned)(64 * sh.W)), sh.smem,
+                       s, A);
+  } else {
+    with_value(QueryLayouts{}, code, [&](auto dc) {
+      constexpr int D = decltype(dc)::value;
+      if constexpr (D != 0 && !OcCode<D>::GEN) {
+        const Shape sh = shape(false, ExCfg<D>::WAVES);
+        const dim3 grid((unsigned)((Q + sh.W - 1) / sh.W)), block((unsigned)(64 * sh.W));
+        auto go = [&](auto kernel) {
+          allow_lds(kernel, sh.smem);
+          hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, A);
+        };
+        if (filtered == 2) go(tail_hash_merge_kernel<D, TAIL_TAGS>);
+        else if (filtered == 1) go(tail_hash_merge_kernel<D, TAIL_BITS>);
+        else go(tail_hash_merge_kernel<D, TAIL_ALL>);
+      }
+    });
+  }
+  HIPCHECK(hipGetLastError());
+}
+
+// Contract: include/ann_hip.h.  Codes by the hash launch itself, then count / scan / place per try.
+extern "C" int annhip_index_hash_tail(annhip_index *ix) {
+  const char *why = tail_refusal(ix, 0);
+  if (!why && (unsigned long long)ix->T * ix->tail_m >= 0xFFFFFFF0ull) why = "tries x tail rows must fit 32 bits";
+  if (why) {
+    fprintf(stderr, "annhip_index_hash_tail: %s\n", why);
+    return -1;
+  }
+  const size_t m = ix->tail_m;
+  if (!m) return 0;
+  HIPCHECK(hipDeviceSynchronize());
+  drop_tail_hash(ix);
+  const size_t items = m * (size_t)ix->T;
+  const u32 stride = (u32)(((size_t)1 << ix->ds) + 1);
+  ix->tail_codes = dev_alloc<u32>(items);
+  ix->tail_off = dev_alloc<u32>((size_t)ix->T * stride);
+  ix->tail_rows = dev_alloc<u32>(items);
+  // the code of a non-aliased fixed-mode query equal to the row: the query path's own hash launch over the tail
+  launch_codes(query_params(ix), m, ix->d_tail, ix->tail_codes, 0);
+  HIPCHECK(hipMemsetAsync(ix->tail_off, 0, sizeof(u32) * (size_t)ix->T * stride, 0));
+  thash_count_kernel<<<grid_for(items, 256, 4096), 256>>>(items, ix->tail_codes, ix->T, stride, ix->tail_off);
+  thash_scan_kernel<<<ix->T, 1024>>>(ix->tail_off, stride, (u32)m);
+  thash_place_kernel<<<grid_for(items, 256, 4096), 256>>>(items, ix->tail_codes, ix->T, stride, ix->tail_off, ix->tail_rows);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipDeviceSynchronize());
+  ix->tail_mh = m;
+  return 0;
 }
 
 // The three exact scans of an index: over the built rows as before, then -- where rows have been appended -- the tail's

@@ -166,7 +166,37 @@ int annhip_index_has_tags(const annhip_index *ix);
  *   annhip_index_reshard drops the tail.  annhip_index_set_fixed(ix, 0) keeps it stored.
  *   NOT covered -- these never see the tail: parity-mode queries, annhip_sh_*, annhip_query_slice, query_gpu,
  *   annhip_index_export, annhip_index_checksum and index files (annhip_save_write).
- * annhip_stats out[3] additionally counts, while profile = 1, the (query, valid tail row) pairs the tail's scan scored. */
+ * annhip_stats out[3] additionally counts, while profile = 1, the (query, valid tail row) pairs the tail's scan scored.
+ *
+ * Hashed tail rows (opt-in; default: none).  The exact scan costs ycnt * m row pairs per step.  annhip_index_hash_tail
+ * files the current tail rows under their hash codes, so that a query fetches only the tail rows of the buckets it probes
+ * anyway; those rows are then found approximately, like built rows, and no longer exactly.  mh = hashed tail rows, 0 <= mh
+ * <= m.  The three tiers: built index | hashed tail [0, mh) | fresh tail [mh, m).
+ * annhip_index_hash_tail: hashes ALL current tail rows and builds the bucket structure over rows [0, m); afterwards mh = m.
+ * Synchronous, on the null stream, as annhip_index_append is.  Returns 0; -1, one line on stderr, nothing changed, wherever
+ * annhip_index_append would refuse a call without rows: fixed mode off, a resharded index (and tries * m >= 0xFFFFFFF0).
+ * m == 0: returns 0 and launches nothing.  Calling it again after more appends rebuilds over all m rows.
+ * annhip_index_tail_hashed: mh.
+ * Rows appended after the call land in [mh, m) and are scanned exactly as before; annhip_index_append does not change.
+ * The code of tail row j in try t, c[j][t], is the hash code a non-aliased fixed-mode query equal to that row gets (the
+ * query path's hash launch over the tail rows).  Hit test: for query q let cq[t] be its codes and, with pair bits b > 0,
+ * o[q][t][0..b) its ranked bits (annhip_probe_bits); bit(s) = 1 << (ds-1-s); PM[q][t] = OR of bit(o[u]), u < b (0 when b = 0);
+ * x = cq[t] ^ c[j][t].  Tail row j HITS in try t iff x == 0, or popcount(x) == 1, or popcount(x) == 2 and (x & ~PM[q][t]) ==
+ * 0: exactly membership of x in the mask set of the probe setting (the last case is empty while b <= 1).  Row j < mh is a
+ * tail candidate of q iff it hits in some try and is valid: allowed by the allow list, passing q's tag test in a tagged
+ * call (the aliased test concerns ids < n only).
+ * With mh > 0 a fixed-mode call (annhip_query, annhip_query_on, annhip_stream_*, annhip_query_tagged, annhip_query_k)
+ * returns the k (or kq) smallest distinct (distance, id) keys among R(q) (pads dropped), the tail candidates among rows
+ * [0, mh), and ALL valid rows of [mh, m); padded with (n_total, +inf); distances are the query path's bits.  With mh == 0
+ * every entry point launches exactly what it launched before.
+ * annhip_index_drop_tail and annhip_index_reshard set mh = 0.  annhip_index_reserve_tail and reallocating appends keep the
+ * structure (it names rows by j).  annhip_index_set_fixed(ix, 0) keeps it.  A change of the probe setting needs no rebuild:
+ * the masks are applied at query time.  Unchanged: annhip_index_exact_query* cover all n_total rows exactly;
+ * annhip_index_copy_rows, export, checksum and index files.  Memory: 8 * tries * mh + 4 * tries * (2^ds + 1) bytes.
+ * annhip_stats out[3] counts the (query, candidate) pairs the hashed lookup scored as well; annhip_stage_ms out[4] spans
+ * both tail launches. */
+int annhip_index_hash_tail(annhip_index *ix);
+size_t annhip_index_tail_hashed(const annhip_index *ix);
 int annhip_index_append(annhip_index *ix, const ftype *rows, int rows_on_device, size_t count, const uint32_t *tags,
                         int tags_on_device);
 int annhip_index_reserve_tail(annhip_index *ix, size_t rows);

@@ -323,6 +323,72 @@ def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, al
     return ids, dists
 
 
+def _radius_dev(radius, Q, dtype, device, what="radius"):
+    """The radii of a batch -> a device tensor [Q] of `dtype` (keep it alive for the call): a Python float, broadcast; a
+    numpy array [Q] of that dtype, copied; or a device tensor [Q] of that dtype, taken as it is.  ValueError for anything
+    else, a wrong dtype or a wrong shape."""
+    import torch
+    if isinstance(radius, bool):
+        raise ValueError("%s must be a float, a numpy array or a device tensor of length %d" % (what, Q))
+    if isinstance(radius, (int, float, np.floating, np.integer)):
+        return torch.full((Q,), float(radius), dtype=dtype, device=device)
+    if isinstance(radius, np.ndarray):
+        if radius.dtype != (np.float32 if dtype == torch.float32 else np.float64):
+            raise ValueError("%s must have the index's dtype" % what)
+        if radius.shape != (Q,):
+            raise ValueError("%s must have length %d" % (what, Q))
+        return torch.from_numpy(np.ascontiguousarray(radius)).to(device)
+    if not isinstance(radius, torch.Tensor) or not radius.is_cuda or radius.dtype != dtype or tuple(radius.shape) != (Q,):
+        raise ValueError("%s must be a float, a numpy array or a device tensor of the index's dtype and length %d" % (what, Q))
+    return radius.contiguous()
+
+
+def _ptr(t, hold):
+    """data_ptr() of a device tensor for a call that refuses NULL arrays; an empty tensor has none, `hold` (never read
+    or written: the batch is empty) stands in for it."""
+    return t.data_ptr() if t.numel() else hold.data_ptr()
+
+
+def radius_trim(ids, dists, radius, pad_id):
+    """annhip_radius_trim: cut a result in (distance, id) order at a radius, in place.  ids int64 [Q,k] and dists [Q,k]
+    contiguous device tensors (query(k=), exact_query(k=) or exact_knn's), radius as Index.query_radius takes it, pad_id the
+    id of a pad (n, or n_total of an index with a tail).  An entry stays iff its id is not pad_id and its distance is <=
+    the query's radius; the rest of the row becomes (pad_id, +inf).  Runs on the current stream.  -> counts int32 [Q]."""
+    import torch
+    if (not isinstance(ids, torch.Tensor) or not isinstance(dists, torch.Tensor) or not ids.is_cuda or not dists.is_cuda
+            or ids.dtype != torch.int64 or dists.dtype not in (torch.float32, torch.float64) or ids.dim() != 2
+            or ids.shape != dists.shape or not ids.is_contiguous() or not dists.is_contiguous()):
+        raise ValueError("radius_trim: ids int64 [Q,k] and dists [Q,k] must be contiguous device tensors of one shape")
+    Q, k = ids.shape
+    rad = _radius_dev(radius, Q, dists.dtype, dists.device)
+    counts = torch.zeros((Q,), dtype=torch.int32, device=ids.device)
+    lib = _lib.load("f32" if dists.dtype == torch.float32 else "f64")
+    if not Q or not k:
+        return counts
+    if lib.annhip_radius_trim(Q, k, int(pad_id), rad.data_ptr(), ids.data_ptr(), dists.data_ptr(), counts.data_ptr(),
+                              torch.cuda.current_stream(ids.device).cuda_stream) != 0:
+        raise ValueError("annhip_radius_trim refused its arguments")
+    return counts
+
+
+def radius_recall(guess_ids, guess_counts, truth_ids, truth_counts):
+    """Recall of a radius query against its ground truth: the mean, over the queries with truth_counts > 0, of
+    |guess[q][:guess_counts[q]] ∩ truth[q][:truth_counts[q]]| / truth_counts[q] -> (recall, queries counted); (0.0, 0) where
+    no query has a true hit.  Integer tensors guess_ids [Q,kg], truth_ids [Q,kt], counts [Q]; pure torch, any device."""
+    import torch
+    dev = guess_ids.device
+    gi, ti = guess_ids.long(), truth_ids.long().to(dev)
+    gc, tc = guess_counts.long().to(dev), truth_counts.long().to(dev)
+    glive = torch.arange(gi.shape[1], device=dev)[None, :] < gc[:, None]  # [Q,kg]
+    tlive = torch.arange(ti.shape[1], device=dev)[None, :] < tc[:, None]  # [Q,kt]
+    hit = ((ti.unsqueeze(2) == gi.unsqueeze(1)) & glive.unsqueeze(1)).any(dim=2) & tlive  # [Q,kt]: truth id found
+    use = tc > 0
+    counted = int(use.sum().item())
+    if not counted:
+        return 0.0, 0
+    return (hit.double().sum(dim=1)[use] / tc[use].double()).mean().item(), counted
+
+
 def recall_at_k(guess, truth):
     """Standard recall@k: the mean over queries of |guess[q] ∩ truth[q]| / k, for integer tensors guess [Q,kg] (as query()
     returns them; ids >= n are its "no neighbour" marks and never match) and truth [Q,k] (exact_knn's ids)."""
@@ -752,6 +818,70 @@ class Index:
         if self.lib.annhip_index_exact_query(self.h, Q, y.data_ptr(), int(bool(alias)), ids.data_ptr(), dists.data_ptr()) != 0:
             raise ValueError("annhip_index_exact_query refused this index (resharded, or k larger than the rows on offer)")
         return ids, dists
+
+    def query_radius(self, y, radius, k=None, alias=False, where=None, ws=None, stream=None):
+        """annhip_query_radius: fixed mode's candidates within a squared-L2 radius, capped at k per query (k=None: the
+        index's k) -> (ids int64 [Q,k], sq dists [Q,k], counts int32 [Q]): rows ascending by (distance, id), padded with
+        (n_total, +inf); counts[q] == k means there may be more.  radius: a Python float, broadcast; a device tensor [Q] of
+        the index's dtype; or a numpy array [Q] of that dtype, copied.  A row is in range iff dist <= radius; a negative or
+        NaN radius matches nothing, +inf gives the row of query(k=k) bit for bit.  where, ws and stream as in query(k=).
+        ValueError for a bool or non-integer k, for a radius of wrong shape or dtype, and where the library refuses (fixed
+        mode off, k outside 1..max_query_k, where= without tags, a resharded index); nothing is launched then."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        k = self.k if k is None else self._check_k(k)
+        if k < 1:
+            raise ValueError("query_radius: k must be at least 1")
+        rad = _radius_dev(radius, Q, y.dtype, y.device)
+        qm = qv = None
+        if where is not None:
+            qm, qv = _where_dev(where, Q, y.device)
+        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        if stream is not None and torch.cuda.current_stream(y.device) != stream:
+            stream.wait_stream(torch.cuda.current_stream(y.device))  # the radius, predicate and output arrays were made on that one
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        rc = self.lib.annhip_query_radius(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
+                                          int(alias), k, _ptr(rad, hold), qm.data_ptr() if qm is not None else None,
+                                          qv.data_ptr() if qv is not None else None, _ptr(ids, hold), dists.data_ptr(),
+                                          counts.data_ptr())
+        if rc == -2:
+            raise ValueError("annhip_query_radius refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
+                             % (k, self.max_query_k))
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in (rad, qm, qv, ids, dists, counts):
+                if t is not None:
+                    t.record_stream(stream)
+        return ids, dists, counts
+
+    def exact_query_radius(self, y, radius, k, alias=False, where=None):
+        """annhip_index_exact_query_radius: the ground truth of query_radius -- exact_query(k=k) cut at the radius ->
+        (ids int64 [Q,k], sq dists [Q,k], counts int32 [Q]), padded with (n_total, +inf).  radius and where as in
+        query_radius.  ValueError as exact_query(k=) raises it, and for a radius of wrong shape or dtype."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        k = self._check_k(k)
+        if k < 1:
+            raise ValueError("exact_query_radius: k must be in 1..1024")
+        rad = _radius_dev(radius, Q, y.dtype, y.device)
+        qm = qv = None
+        if where is not None:
+            qm, qv = _where_dev(where, Q, y.device)
+        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        if self.lib.annhip_index_exact_query_radius(self.h, Q, y.data_ptr(), int(bool(alias)), k, _ptr(rad, hold),
+                                                    qm.data_ptr() if qm is not None else None,
+                                                    qv.data_ptr() if qv is not None else None, _ptr(ids, hold),
+                                                    _ptr(dists, hold), counts.data_ptr()) != 0:
+            raise ValueError("annhip_index_exact_query_radius refused k=%d (k outside 1..1024 or larger than the rows on "
+                             "offer, no tags, or a resharded index)" % k)
+        return ids, dists, counts
 
     def host_stream(self, max_ycnt, lanes=3):
         """annhip_stream_open: pipeline for host-resident (numpy) batches; see HostStream."""

@@ -29,6 +29,7 @@
 #include "ann_filter_kernels.h"
 #include "ann_tag_kernels.h"
 #include "ann_kq_kernels.h"
+#include "ann_radius_kernels.h"
 #include "ann_tail_kernels.h"
 #include "ann_tail_hash_kernels.h"
 
@@ -1913,6 +1914,152 @@ extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip
                       dists_dev);
 }
 
+// ----------------------------------------------------------------------------- radius queries (annhip_query_radius)
+// Contract: include/ann_hip.h.  Kernels: ann_radius_kernels.h.
+// Stage 1 of a radius query: launch_stage1_filter's shape (wave rule, profiling events, s1_launches) with
+// stage1_radius_kernel, for every pair-bit setting, with or without an allow list (bits) and tags (tq).
+static void launch_stage1_radius(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
+                                 const unsigned char *pbits, int pb, const FT *radius, const u32 *bits, FT *cand_d, u32 *cand_i,
+                                 u32 *nvt, u32 *nvo, hipStream_t s, const TagQuery *tq) {
+  if (!Q) return;
+  const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
+  size_t slots = 0;
+  for (int t = 0; t < P.T; t++) slots += (size_t)rpt * ix->h_tries[t].pm;
+  int W = (int)std::min<size_t>(4, std::max<size_t>(1, slots / ANN_S1_CHUNK));
+  if (env().s1_waves) W = env().s1_waves;
+  const int K1 = P.k + 1, cap = stage1_cap(W, K1);
+  const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
+  EventPair ev;
+  const bool prof = ix->profile;
+  if (prof) {
+    if (ix->ev_free.empty()) {
+      HIPCHECK(hipEventCreate(&ev.a));
+      HIPCHECK(hipEventCreate(&ev.b));
+    } else {
+      ev = ix->ev_free.back();
+      ix->ev_free.pop_back();
+    }
+    HIPCHECK(hipEventRecord(ev.a, s));
+  }
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
+    with_rows(P, [&](auto rt) {
+      auto launch = [&](auto sg) {
+        constexpr int D = decltype(dd)::value;
+        constexpr bool SG = decltype(sg)::value;
+        using RT = typename decltype(rt)::type;
+        allow_lds(stage1_radius_kernel<D, SG, RT>, smem);
+        hipLaunchKernelGGL((stage1_radius_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
+                           pb, rpt, radius, tq ? tq->tags : (const u32 *)NULL, bits, tq ? tq->qmask : (const u32 *)NULL,
+                           tq ? tq->qvalue : (const u32 *)NULL, K1, cap, cand_d, cand_i, nvt, nvo);
+      };
+      if (ix->use_seg) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
+  });
+  HIPCHECK(hipGetLastError());
+  if (prof) {
+    HIPCHECK(hipEventRecord(ev.b, s));
+    ix->ev_used.push_back(ev);
+    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
+  }
+  ix->s1_launches += 1;
+}
+
+static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *radius, size_t *ids, FT *dists, u32 *counts,
+                               hipStream_t s) {
+  if (!Q || !kcap) return;
+  const size_t blocks = (Q + 3) / 4;  // one wave per row, 4 rows per workgroup
+  if (blocks > 0x7FFFFFFFull) die("radius trim: batch too large");
+  hipLaunchKernelGGL(radius_trim_kernel, dim3((unsigned)blocks), dim3(256), 0, s, Q, kcap, pad_id, radius, ids, dists, counts);
+  HIPCHECK(hipGetLastError());
+}
+
+// query_k_impl with stage1_radius_kernel in stage 1 and the trim at the end (the caller has validated everything)
+static long query_radius_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
+                              size_t kcap, const FT *radius, const TagQuery *tq, size_t *ids_dev, ftype *dists_dev,
+                              u32 *counts_dev) {
+  if (!Q) return 0;
+  if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
+  const QParams P = query_params(ix);
+  QParams P1 = P;  // stage 1's view: k = kcap
+  P1.k = (int)kcap;
+  if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
+  const FT *y = reinterpret_cast<const FT *>(y_dev);
+  const int K1 = (int)kcap + 1;
+  std::vector<hipEvent_t> marks_store, *marks = ix->profile == 1 ? &marks_store : NULL;
+  seg_mark(ix, marks, s);
+  const bool probing = ix->probe > 0;
+  unsigned char *pbits = NULL;
+  u32 *codes = (u32 *)ws.codes.need(sizeof(u32) * Q * P.T);
+  if (probing) {
+    pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
+    launch_codes_probe(P, Q, y, codes, pbits, ix->probe, s, ws.d_fcount);
+  } else {
+    launch_codes(P, Q, y, codes, s, ws.d_fcount);
+  }
+  seg_mark(ix, marks, s);
+  u32 *top_i = (u32 *)ws.top_i.need(sizeof(u32) * Q * kcap);
+  FT *top_d = (FT *)ws.top_d.need(sizeof(FT) * Q * kcap);
+  FT *cand_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * K1);
+  u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
+  u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
+  u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
+  launch_stage1_radius(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, radius, ix->filter, cand_d, cand_i, nvt, nvo, s,
+                       tq);
+  seg_mark(ix, marks, s);
+  hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kcap, K1, P.L1, P.P1,
+                     cand_d, cand_i, nvt, top_i, top_d, (int)kcap, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
+  HIPCHECK(hipGetLastError());
+  seg_mark(ix, marks, s);
+  FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kcap);
+  launch_stage2_kq(P, Q, y, alias, top_i, top_d, kcap, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL,
+                   s);
+  seg_mark(ix, marks, s);
+  if (ix->tail_mh)
+    launch_tail_hash_merge(ix, Q, y, kcap, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
+                           ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+  if (ix->tail_m > ix->tail_mh)
+    launch_tail_merge(ix, Q, y, alias, kcap, tq, kcap, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL,
+                      s, ix->tail_mh);
+  // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
+  // so the trim is in neither the stage-1 nor the stage-2 figure)
+  launch_radius_trim(Q, kcap, n_total(ix), radius, ids_dev, out_d, counts_dev, s);
+  seg_mark(ix, marks, s);
+  seg_mark(ix, marks, s);
+  if (marks) ix->seg_used.push_back(marks_store);
+  ix->queries += (double)Q;
+  return 0;
+}
+
+// A refusal launches nothing and leaves the outputs untouched; this entry never aborts on what it can refuse.
+extern "C" long annhip_query_radius(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev,
+                                    int alias, size_t kcap, const ftype *radius_dev, const uint32_t *qmask_dev,
+                                    const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
+  const bool tagged = qmask_dev && qvalue_dev;
+  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
+                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                    : !radius_dev ? "radius_dev must be given"
+                    : !ids_dev ? "ids_dev must be given"
+                    : (qmask_dev != NULL) != (qvalue_dev != NULL) ? "qmask_dev and qvalue_dev must both be given, or neither"
+                    : tagged && !ix->tags ? "the index has no tags (annhip_index_set_tags)"
+                    : !query_k_fits(make_params(ix), kcap) ? "kcap outside 1..annhip_index_max_query_k" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_query_radius: %s\n", why);
+    return -2;
+  }
+  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  return query_radius_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kcap,
+                           reinterpret_cast<const FT *>(radius_dev), tagged ? &tq : NULL, ids_dev, dists_dev, counts_dev);
+}
+
+extern "C" int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev,
+                                  ftype *dists_dev, uint32_t *counts_dev, void *hip_stream) {
+  if (!radius_dev || !ids_dev || !dists_dev) return -1;
+  launch_radius_trim(ycnt, kcap, pad_id, reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
+                     counts_dev, (hipStream_t)hip_stream);
+  return 0;
+}
+
 extern "C" long annhip_query_slice(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, size_t q_lo, size_t nq,
                                    const ftype *y_slice_dev, const uint32_t *codes_all_dev, int alias, size_t *ids_dev,
                                    ftype *dists_dev) {
@@ -2773,6 +2920,21 @@ extern "C" int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const f
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
   return index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qvalue_dev, ids_dev, dists_dev);
+}
+
+// Contract: include/ann_hip.h.  annhip_index_exact_query_k's path, then the trim (ann_radius_kernels.h): the ground truth of
+// annhip_query_radius.  Synchronous, on the null stream.
+extern "C" int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kcap,
+                                               const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qvalue_dev,
+                                               size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
+  if (!radius_dev || !ids_dev || !dists_dev) return exact_refuse("radius_dev, ids_dev and dists_dev must all be given");
+  if (const int rc = annhip_index_exact_query_k(ix, ycnt, y_dev, alias, kcap, qmask_dev, qvalue_dev, ids_dev, dists_dev)) return rc;
+  launch_radius_trim(ycnt, kcap, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
+                     counts_dev, 0);
+  HIPCHECK(hipStreamSynchronize(0));
+  return 0;
 }
 
 // ----------------------------------------------------------------------------- precomp

@@ -532,6 +532,53 @@ int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *
 int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
                                const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 
+/* ---- radius queries: every candidate within r, capped --------------------------------------------------------------- */
+/* All distances and radii are squared L2 in ftype, like every distance the library returns.  Row i is IN RANGE for query q
+ * iff dist(q, i) <= radius[q], compared as floating-point values: -0.0 counts as 0; a negative or NaN radius puts nothing
+ * in range; +inf puts every row in range, including rows whose distance overflowed to +inf.  A row whose distance is NaN
+ * (inf - inf on rows that overflowed) is in range for no radius, +inf included.
+ * annhip_query_radius: a fixed-mode call with the shape of annhip_query_k.  "Valid" is read exactly as there (id < n, the
+ * allow list, the tag test, not the query itself when aliased) and the probed buckets are the same, for every pair-bit
+ * setting.  With "smallest" meaning smallest distinct (distance, id) keys:
+ *   S1 = the kcap smallest among the valid in-range ids of the probed buckets;
+ *   S2 = the kcap smallest among S1 and the valid in-range graph neighbours graph[p][z], z < kg, of the members p of S1;
+ *   S3 = the kcap smallest among S2 and the in-range tail candidates (hashed tier: the rows that pass the hit test of
+ *        "Hashed tail rows"; fresh tier: all valid rows);
+ *   output: ids_dev size_t[ycnt][kcap], dists_dev ftype[ycnt][kcap] (may be NULL) = S3 ascending, padded with
+ *        (n_total, +inf); counts_dev u32[ycnt] (may be NULL), counts[q] = |S3|.  counts[q] == kcap means "there may be
+ *        more: ask again with a larger kcap".
+ * Two equalities follow and are part of the contract: with radius[q] = +inf the row is, bit for bit, the row of
+ * annhip_query_k(kq = kcap), and counts[q] is its number of non-pad entries; with kcap == kg as well, it is the row of the
+ * plain fixed-mode call.  The one exception: a row whose distance is NaN, which annhip_query_k keeps behind every other key
+ * and which no radius admits -- the equalities hold for every query without such a row among its candidates.
+ * radius_dev ftype[ycnt]; qmask_dev / qvalue_dev both NULL (untagged) or both given (u32[ycnt] each).  ws and hip_stream
+ * as in annhip_query_k.  Asynchronous; returns 0.  Returns -2, with one line on stderr, nothing launched and the outputs
+ * untouched: while fixed mode is off; on a resharded index; for kcap == 0 or kcap > annhip_index_max_query_k(ix); for
+ * radius_dev == NULL or ids_dev == NULL, whatever ycnt is; when exactly one predicate array is given; for a tagged call on
+ * an index without tags.  ycnt == 0 (with arguments that pass these tests) returns 0.  Composes with annhip_index_set_probe, annhip_index_set_filter, tags, annhip_index_set_rows,
+ * alias, and several workspaces on several streams.  NOT covered: parity mode, annhip_stream_*, annhip_sh_*,
+ * annhip_query_slice, query_gpu.  Every existing entry point launches exactly what it launched before.
+ * Only in-range keys ever enter a selection buffer of stage 1 (its admission threshold starts at the radius), and stage 2
+ * loads graph rows for the in-range results only (a pad has no neighbours).  What a step costs beside annhip_query_k
+ * followed by annhip_radius_trim is measured, not promised: DESIGN.md section 6, tools/radius_bench.py.
+ * annhip_index_exact_query_radius: the ground truth -- the kcap smallest (distance, id) among ALL valid in-range rows of
+ * the n_total rows, i.e. annhip_index_exact_query_k(kq = kcap) trimmed.  Non-zero with the outputs untouched: that call's
+ * refusals (a resharded index and exactly one predicate array are tested first, then NULL arrays, then kcap and the tags),
+ * and a NULL radius_dev, ids_dev or dists_dev, whatever ycnt is.  Pads and counts as above.  Synchronous.
+ * annhip_radius_trim: the one small kernel both calls end with, exported so that any [ycnt][kcap] result in (distance, id)
+ * order can be trimmed (annhip_exact_knn's included).  An entry stays iff id != pad_id and it is in range; everything
+ * after the last kept entry becomes (pad_id, +inf); counts_dev[q] (may be NULL) = entries kept.  A pad is told by its id,
+ * not by its distance.  In place, on hip_stream; returns 0.  ids_dev, dists_dev and radius_dev must be non-NULL, whatever
+ * ycnt and kcap are: -1 otherwise, nothing launched.  ycnt == 0 or kcap == 0 launches nothing and returns 0. */
+long annhip_query_radius(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                         size_t kcap, const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qvalue_dev,
+                         size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev);
+int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kcap,
+                                    const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qvalue_dev,
+                                    size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev);
+int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev, ftype *dists_dev,
+                       uint32_t *counts_dev, void *hip_stream);
+
 /* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /
  * rand_norm produce (/root/reference/time_results.c:10-13, randNorm.c:9-21), incl. the pending second value of a pair

@@ -5,7 +5,7 @@ mirror of the reference's interface used by the tests, the bench and multi-GPU h
 """
 from . import _lib
 from .api import (HostStream, Index, Save, checksum, exact_knn, gpu_cleanup, gpu_init, precomp, query, radius_recall, radius_trim,
-                  recall_at_k, recall_ranks, recall_summary, synth_randnorm)
+                  recall_at_k, recall_ranks, recall_summary, rerank, synth_randnorm)
 
-__all__ = ["HostStream", "Index", "Save", "precomp", "query", "recall_ranks", "recall_summary", "exact_knn", "recall_at_k", "radius_trim", "radius_recall", "gpu_init", "gpu_cleanup", "synth_randnorm", "checksum",
+__all__ = ["HostStream", "Index", "Save", "precomp", "query", "recall_ranks", "recall_summary", "exact_knn", "recall_at_k", "radius_trim", "radius_recall", "rerank", "gpu_init", "gpu_cleanup", "synth_randnorm", "checksum",
            "_lib"]

@@ -349,6 +349,58 @@ def _ptr(t, hold):
     return t.data_ptr() if t.numel() else hold.data_ptr()
 
 
+def _check_cand(what, cand, Q, device):
+    """cand of a rerank call: a contiguous int64 [Q, C] device tensor -> C; ValueError for anything else"""
+    import torch
+    if (not isinstance(cand, torch.Tensor) or not cand.is_cuda or cand.dtype != torch.int64 or cand.dim() != 2
+            or cand.shape[0] != Q or not cand.is_contiguous() or cand.device != device):
+        raise ValueError("%s: cand must be a contiguous int64 [Q, C] device tensor with one row per query" % what)
+    return int(cand.shape[1])
+
+
+def _rerank_out(what, out_ids, out_dists, Q, k, dtype, device):
+    import torch
+    ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=device)
+    dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=dtype, device=device)
+    if (tuple(ids.shape) != (Q, k) or tuple(dists.shape) != (Q, k) or ids.dtype != torch.int64 or dists.dtype != dtype
+            or not ids.is_cuda or not dists.is_cuda or not ids.is_contiguous() or not dists.is_contiguous()):
+        raise ValueError("%s: out_ids int64 [Q,k] and out_dists [Q,k] must be contiguous device tensors" % what)
+    return ids, dists
+
+
+def rerank(points, y, cand, k, out_ids=None, out_dists=None):
+    """annhip_rerank: the exact top-k of caller-supplied candidates.  Torch device tensors points [n,d], y [Q,d] and cand,
+    a contiguous int64 [Q,C] tensor of row ids -> (ids int64 [Q,k], sq dists [Q,k]): per query the k smallest
+    (distance, id) among its distinct candidates below n, ascending, padded with (n, +inf).  An entry >= n (a pad, -1,
+    anything) is skipped; a repeated id counts once; k may exceed C.  The distances are bit for bit exact_knn's and the
+    query path's.  Precision from the dtype; runs on the current stream and returns at once.  out_ids may be cand where
+    C == k.  ValueError for a mixed or unsupported dtype, for a cand that is not a contiguous int64 [Q,C] device tensor,
+    and where the library refuses (k or C outside 1..1024, d == 0, a row too long for the LDS of one CU); the outputs are
+    then untouched."""
+    import torch
+    if (not isinstance(points, torch.Tensor) or not isinstance(y, torch.Tensor) or points.dtype != y.dtype
+            or points.dtype not in (torch.float32, torch.float64)):
+        raise ValueError("rerank: points and y must both be float32 or both float64")
+    if points.dim() != 2 or y.dim() != 2 or points.shape[1] != y.shape[1] or not points.is_cuda or not y.is_cuda:
+        raise ValueError("rerank: points [n,d] and y [Q,d] must be device tensors with the same d")
+    Q = y.shape[0]
+    C_ = _check_cand("rerank", cand, Q, y.device)
+    k = Index._check_k(k)
+    if k < 0:
+        raise ValueError("rerank: k must be in 1..1024")
+    lib = _lib.load("f32" if points.dtype == torch.float32 else "f64")
+    points, y = points.contiguous(), y.contiguous()
+    ids, dists = _rerank_out("rerank", out_ids, out_dists, Q, k, y.dtype, y.device)
+    hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+    rc = lib.annhip_rerank(points.shape[0], points.shape[1], _ptr(points, hold), Q, _ptr(y, hold), C_, _ptr(cand, hold), k,
+                           _ptr(ids, hold), _ptr(dists, hold), torch.cuda.current_stream(y.device).cuda_stream)
+    if rc != 0:
+        raise ValueError("annhip_rerank refused n=%d d=%d C=%d k=%d (k or C outside 1..1024, d == 0, ids beyond 32 bits, or a "
+                         "row too long for the LDS of one CU)"
+                         % (points.shape[0], points.shape[1], C_, k))
+    return ids, dists
+
+
 def radius_trim(ids, dists, radius, pad_id):
     """annhip_radius_trim: cut a result in (distance, id) order at a radius, in place.  ids int64 [Q,k] and dists [Q,k]
     contiguous device tensors (query(k=), exact_query(k=) or exact_knn's), radius as Index.query_radius takes it, pad_id the
@@ -818,6 +870,55 @@ class Index:
         if self.lib.annhip_index_exact_query(self.h, Q, y.data_ptr(), int(bool(alias)), ids.data_ptr(), dists.data_ptr()) != 0:
             raise ValueError("annhip_index_exact_query refused this index (resharded, or k larger than the rows on offer)")
         return ids, dists
+
+    def rerank(self, y, cand, k=None, stream=None, out_ids=None, out_dists=None):
+        """annhip_index_rerank: the exact top-k of caller-supplied candidates on the index's NATIVE rows (whatever set_rows
+        says, fixed mode on or off).  y [Q,d], cand a contiguous int64 [Q,C] device tensor of row ids over [0, n_total):
+        the built rows, then the tail -> (ids int64 [Q,k], sq dists [Q,k]), the k smallest (distance, id) among each
+        query's distinct in-range candidates, padded with (n_total, +inf).  Entries >= n_total are skipped, a repeated id
+        counts once, k may exceed C; k=None: the index's k.  No allow list, tags, probe or alias rule applies: the caller
+        chose the candidates.  Distances are bit for bit query()'s and exact_query()'s on native rows.  Runs on `stream`
+        (the null stream when none is given) and returns at once; out_ids may be cand where C == k.  ValueError for a
+        cand that is not a contiguous int64 [Q,C] device tensor, a bool or non-integer k, and where the library refuses
+        (k or C outside 1..1024, a row too long for the LDS of one CU, a resharded index); nothing is launched then and
+        the outputs are untouched."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        C_ = _check_cand("Index.rerank", cand, Q, y.device)
+        k = self.k if k is None else self._check_k(k)
+        if k < 0:
+            raise ValueError("Index.rerank: k must be in 1..1024")
+        ids, dists = _rerank_out("Index.rerank", out_ids, out_dists, Q, k, y.dtype, y.device)
+        cur = torch.cuda.current_stream(y.device)
+        if stream is not None and cur != stream:
+            stream.wait_stream(cur)  # the candidate and output arrays were made on that one
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        rc = self.lib.annhip_index_rerank(self.h, stream.cuda_stream if stream is not None else None, Q, _ptr(y, hold), C_,
+                                          _ptr(cand, hold), k, _ptr(ids, hold), _ptr(dists, hold))
+        if rc != 0:
+            raise ValueError("annhip_index_rerank refused C=%d k=%d (k or C outside 1..1024, a row too long for the LDS of one "
+                             "CU, or a resharded index)" % (C_, k))
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in (y, cand, ids, dists, hold):
+                t.record_stream(stream)
+        return ids, dists
+
+    def query_reranked(self, y, k=None, oversample=2, alias=False, where=None, ws=None, stream=None):
+        """query(k=min(max_query_k, k * oversample)) on the rows the index is set to, then rerank(..., k) of those
+        candidates on the native rows, both on `stream` -> (ids int64 [Q,k], sq dists [Q,k]).  With narrow rows
+        (set_rows) this is the usual two-step scheme: search the cheap rows for a few more candidates than needed, re-score
+        them at full precision; the distances that come back are the native rows'.  k=None: the index's k.  Fixed mode
+        only, as query(k=); alias, where, ws and stream as there (they shape the candidates; rerank itself tests nothing).
+        ValueError for oversample < 1 or a non-integer oversample, and as query(k=) and rerank raise it."""
+        if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
+            raise ValueError("query_reranked: oversample must be an integer >= 1, got %r" % (oversample,))
+        k = self.k if k is None else self._check_k(k)
+        if k < 1:
+            raise ValueError("query_reranked: k must be at least 1")
+        kq = min(self.max_query_k, k * int(oversample))
+        cand, _, _ = self.query(y, alias=alias, ws=ws, stream=stream, where=where, k=kq)
+        return self.rerank(y, cand, k=k, stream=stream)
 
     def query_radius(self, y, radius, k=None, alias=False, where=None, ws=None, stream=None):
         """annhip_query_radius: fixed mode's candidates within a squared-L2 radius, capped at k per query (k=None: the

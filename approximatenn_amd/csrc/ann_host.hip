@@ -32,6 +32,7 @@
 #include "ann_radius_kernels.h"
 #include "ann_tail_kernels.h"
 #include "ann_tail_hash_kernels.h"
+#include "ann_rerank_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -2935,6 +2936,87 @@ extern "C" int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, co
                      counts_dev, 0);
   HIPCHECK(hipStreamSynchronize(0));
   return 0;
+}
+
+// ----------------------------------------------------------------------------- rerank (annhip_rerank)
+// Contract: include/ann_hip.h.  Kernels: ann_rerank_kernels.h.  One wave per query; LDS per wave: one selection buffer of
+// exact_shape()'s cap plus k keys, the any-d form's query and tree scratch, the id list; the waves come down until the
+// workgroup fits.  No workspace, nothing synchronised: the launch goes to s and the call returns.
+static int rerank_refuse(const char *who, const char *why) {
+  fprintf(stderr, "%s: %s\n", who, why);
+  return -1;
+}
+static int launch_rerank(const char *who, size_t n, size_t m, size_t d, const FT *points, const FT *tail, size_t Q, const FT *y,
+                         size_t ccnt, const size_t *cand, size_t k, size_t *ids, FT *dists, hipStream_t s) {
+  if (k < 1 || k > 1024) return rerank_refuse(who, "k must be in 1..1024");
+  if (ccnt < 1 || ccnt > 1024) return rerank_refuse(who, "ccnt must be in 1..1024");
+  if (d < 1) return rerank_refuse(who, "d must be at least 1");
+  if (n + m >= 0xFFFFFFF0ull || n + m < n) return rerank_refuse(who, "row ids must fit 32 bits");
+  if (Q >= 0xFFFFFFF0ull) return rerank_refuse(who, "ycnt must fit 32 bits");
+  const int code = layout_code(d);
+  const bool generic = layout_is_generic(code);
+  struct Shape {
+    size_t W, smem, cap;
+  };
+  auto shape = [&](int max_waves) {
+    ExShape sh;
+    (void)exact_shape(d, k, generic, max_waves, false, 0, sh);  // for cap: no row tile here, the fit is tested below
+    size_t np = ANN_EX_GEN_ELEMS / d;
+    np = np < 1 ? 1 : (np > ANN_WAVE ? ANN_WAVE : np);
+    const size_t wave_bytes = sizeof(Key) * (sh.cap + k) + (generic ? (((1 + np) * d * sizeof(FT) + 15) & ~(size_t)15) : 0) +
+                              sizeof(u32) * rerank_wave_words(ccnt);
+    Shape r{(size_t)max_waves, 0, sh.cap};
+    while (r.W > 1 && r.W * wave_bytes > ANN_EX_LDS_BUDGET) r.W--;
+    r.smem = r.W * wave_bytes;
+    return r;
+  };
+  int max_waves = ANN_EX_GEN_WAVES;
+  if (!generic)
+    with_value(QueryLayouts{}, code, [&](auto dc) {
+      constexpr int D = decltype(dc)::value;
+      if constexpr (D != 0 && !OcCode<D>::GEN) max_waves = ExCfg<D>::WAVES;
+    });
+  const Shape sh = shape(max_waves);
+  if (sh.smem > 160 * 1024) return rerank_refuse(who, "row too long for the LDS of one CU");
+  if (!Q) return 0;
+  gpu_init();
+  RerankArgs A = {};
+  A.t.tail = tail, A.t.y = y, A.t.out_ids = ids, A.t.out_d = dists;
+  A.t.n = (u32)n, A.t.m = (u32)m, A.t.Q = (u32)Q;
+  A.t.d = (int)d, A.t.k = (int)k, A.t.kin = 0, A.t.cap = (int)sh.cap;
+  A.points = points, A.cand = cand, A.ccnt = (int)ccnt;
+  const dim3 grid((unsigned)((Q + sh.W - 1) / sh.W)), block((unsigned)(64 * sh.W));
+  if (generic) {
+    allow_lds(rerank_generic_kernel, sh.smem);
+    hipLaunchKernelGGL(rerank_generic_kernel, grid, block, sh.smem, s, A);
+  } else {
+    with_value(QueryLayouts{}, code, [&](auto dc) {
+      constexpr int D = decltype(dc)::value;
+      if constexpr (D != 0 && !OcCode<D>::GEN) {
+        allow_lds(rerank_kernel<D>, sh.smem);
+        hipLaunchKernelGGL(rerank_kernel<D>, grid, block, sh.smem, s, A);
+      }
+    });
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int annhip_rerank(size_t n, size_t d, const ftype *points_dev, size_t ycnt, const ftype *y_dev, size_t ccnt,
+                             const size_t *cand_dev, size_t k, size_t *ids_dev, ftype *dists_dev, void *hip_stream) {
+  return launch_rerank("annhip_rerank", n, 0, d, reinterpret_cast<const FT *>(points_dev), NULL, ycnt,
+                       reinterpret_cast<const FT *>(y_dev), ccnt, cand_dev, k, ids_dev, reinterpret_cast<FT *>(dists_dev),
+                       (hipStream_t)hip_stream);
+}
+
+// The built rows, then the tail (id n + j, hashed or not): always the NATIVE rows, fixed mode on or off.
+extern "C" int annhip_index_rerank(annhip_index *ix, void *hip_stream, size_t ycnt, const ftype *y_dev, size_t ccnt,
+                                   const size_t *cand_dev, size_t k, size_t *ids_dev, ftype *dists_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n)
+    return rerank_refuse("annhip_index_rerank", "the index does not hold rows [0, n) on this device (resharded)");
+  return launch_rerank("annhip_index_rerank", ix->n, ix->tail_m, ix->d, ix->d_points, ix->d_tail, ycnt,
+                       reinterpret_cast<const FT *>(y_dev), ccnt, cand_dev, k, ids_dev, reinterpret_cast<FT *>(dists_dev),
+                       (hipStream_t)hip_stream);
 }
 
 // ----------------------------------------------------------------------------- precomp

@@ -532,6 +532,34 @@ int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *
 int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
                                const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev);
 
+/* ---- rerank: the exact top-k of caller-supplied candidates on native rows ------------------------------ */
+/* The second step of "search cheap rows for a few more candidates than needed, re-score them on the full-precision rows",
+ * and the scorer of any id list the caller brings (a keyword index's hits, ids saved from an earlier query).
+ * `rows` below is n for annhip_rerank and n_total = n + m for annhip_index_rerank, which covers the built rows and then the
+ * tail: tail row j has id n + j, whether or not it is hashed.
+ * Candidates: cand_dev[q * ccnt + c] is a row id in the size_t / int64 layout the query calls return.  An entry >= rows
+ * is skipped and never dereferenced -- pads and any other value, an int64 -1 included; the comparison is made on all 64
+ * bits before anything is narrowed (2^32 + 5 is not row 5).  An id that occurs more than once in a query's list counts
+ * once.
+ * Output: per query the k smallest (distance, id) keys among its distinct in-range candidates, ascending, ties broken by
+ * id, padded with (rows, +inf) where there are fewer than k.  k may exceed ccnt.
+ * Distances come out of the same trees as annhip_exact_knn: bit for bit what the query calls and annhip_exact_knn return
+ * for the same (query, row) pair on native rows.  +inf (overflow) is an ordinary value and ranks before the pads.  NaN:
+ * unspecified, as in annhip_exact_knn.
+ * annhip_index_rerank always reads the NATIVE rows, whatever annhip_index_set_rows says (as annhip_index_exact_query
+ * does), with fixed mode on or off.  Neither call consults the allow list, the tags, the probe setting or any alias rule:
+ * the caller chose the candidates.
+ * Runs on hip_stream (NULL: the null stream), needs no workspace, synchronises nothing and may run beside query batches on
+ * other streams.  ids_dev may be cand_dev itself where ccnt == k (query, then rerank in place).  Device pointers; 0 = the
+ * launch is queued.
+ * Returns -1, with one line on stderr, nothing launched and the outputs untouched: k outside 1..1024; ccnt outside
+ * 1..1024; d == 0; rows >= 0xFFFFFFF0; a row too long for the LDS of one CU; annhip_index_rerank on a resharded index.
+ * ycnt == 0 (with arguments that pass these tests) returns 0 and launches nothing. */
+int annhip_rerank(size_t n, size_t d, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                  size_t ccnt, const size_t *cand_dev, size_t k, size_t *ids_dev, ftype *dists_dev, void *hip_stream);
+int annhip_index_rerank(annhip_index *ix, void *hip_stream, size_t ycnt, const ftype *y_dev,
+                        size_t ccnt, const size_t *cand_dev, size_t k, size_t *ids_dev, ftype *dists_dev);
+
 /* ---- radius queries: every candidate within r, capped --------------------------------------------------------------- */
 /* All distances and radii are squared L2 in ftype, like every distance the library returns.  Row i is IN RANGE for query q
  * iff dist(q, i) <= radius[q], compared as floating-point values: -0.0 counts as 0; a negative or NaN radius puts nothing

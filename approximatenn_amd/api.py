@@ -749,6 +749,22 @@ class Index:
         code = int(self.lib.annhip_index_rows(self.h))
         return {v: k for k, v in self.ROWS_BY_PREC[self.prec].items()}.get(code, code)
 
+    PRUNE = {"off": 0, "on": 1, "auto": -1}
+
+    def set_prune(self, mode):
+        """annhip_index_set_prune: the parity path's stage 1 on half the bytes with the same answers (f32 indexes) --
+        "auto" (the default: on for large eligible indexes), "on" (wherever eligible), "off"; or True / False / -1, 0, 1.
+        ValueError where the library refuses (an f64 index, a resharded one, appended rows, k > 31, a row that overflows
+        binary16); the setting is then unchanged."""
+        code = self.PRUNE.get(mode) if isinstance(mode, str) else int(mode)
+        if code is None or self.lib.annhip_index_set_prune(self.h, code) != 0:
+            raise ValueError("annhip_index_set_prune refused mode=%r for this index (%s)" % (mode, self.prec))
+
+    @property
+    def prune(self):
+        """annhip_index_prune: True while this index's parity-mode queries take the pruned stage 1."""
+        return bool(self.lib.annhip_index_prune(self.h))
+
     def workspace(self):
         """annhip_workspace_create: scratch for one in-flight batch (pass to query(ws=..., stream=...))."""
         ws = self.lib.annhip_workspace_create(self.h)
@@ -999,7 +1015,8 @@ class Index:
         out = (C.c_double * 8)()
         self.lib.annhip_stats(self.h, C.byref(out), int(reset))
         return dict(s1_launches=out[0], s1_ms=out[1], s1_rows=out[2], other_rows=out[3], exact_queries=out[4],
-                    queries=out[5], tie_queries=out[6])  # tie_queries: flagged queries answered without the network (ann_tie.h)
+                    queries=out[5], tie_queries=out[6],  # tie_queries: flagged queries answered without the network (ann_tie.h)
+                    uncertified_queries=out[7])         # set_prune: flagged because the certificate failed
 
     def stage_ms(self):
         out = (C.c_double * 6)()

@@ -33,6 +33,7 @@
 #include "ann_tail_kernels.h"
 #include "ann_tail_hash_kernels.h"
 #include "ann_rerank_kernels.h"
+#include "ann_prune_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -92,6 +93,8 @@ struct EnvCfg {
   int tie = 1;          // ANN_HIP_TIE: 0 = flagged rows always take the literal network (no tie path, ann_tie.h)
   int rows = 0;         // ANN_HIP_ROWS: f16 / f32 = query_gpu's resident single-device index reads narrow rows (annhip_index_set_rows)
   int exact_ranges = 0;  // ANN_HIP_EXACT_RANGES: row ranges of annhip_exact_knn's scan (0 = from n, ycnt and the CU count; tests)
+  int prune = -1;        // ANN_HIP_PRUNE: annhip_index_set_prune's mode of a new index (-1 auto, 0 off, 1 on where eligible)
+  int prune_k = 0;       // ANN_HIP_PRUNE_K: keys the preselection keeps per query (0 = max(16, 3 (k+1) / 2); A/B)
   bool rows_warned = false;  // ... and the one warning where it cannot (the other library's type, sharded modes) has been printed
 };
 static EnvCfg g_env;
@@ -126,6 +129,9 @@ static void load_env() {
   c.s2_multi = env_int("ANN_HIP_S2_MULTI", 1);
   c.fin_tail = env_int("ANN_HIP_FIN_TAIL", 1);
   c.exact_ranges = std::max(0, env_int("ANN_HIP_EXACT_RANGES", 0));
+  c.prune = env_int("ANN_HIP_PRUNE", -1);
+  if (c.prune < -1 || c.prune > 1) c.prune = -1;
+  c.prune_k = std::max(0, env_int("ANN_HIP_PRUNE_K", 0));
   const char *rw = getenv("ANN_HIP_ROWS");
   c.rows = !rw ? ANNHIP_ROWS_NATIVE : !strcmp(rw, "f16") ? ANNHIP_ROWS_F16 : !strcmp(rw, "f32") ? ANNHIP_ROWS_F32 : ANNHIP_ROWS_NATIVE;
   const char *cm = getenv("ANN_HIP_CACHE");
@@ -322,6 +328,11 @@ struct annhip_index {
   int probe = 0;          // annhip_index_set_probe: pair bits b of fixed mode (0 = own bucket + Hamming distance 1 only)
   int rows = ANNHIP_ROWS_NATIVE;  // annhip_index_set_rows: which copy of the point rows the single-device query reads
   RN *d_points_h = NULL;          // narrow copy of the rows (made on the first ANNHIP_ROWS_NARROW, kept until destroy/reshard)
+  // annhip_index_set_prune (ann_prune_kernels.h): parity-mode stage 1 preselects on d_points_h and rescores on native rows
+  int prune = -1;                 // the mode asked for: -1 auto, 0 off, 1 on where eligible
+  bool prune_ready = false;       // d_points_h and prune_E are made and the index qualifies (prune_active: and the query does)
+  double prune_E = 0;             // >= max over the rows of ||p - h(p)||_2
+  int prune_kp = 0;               // keys the preselection keeps per query
   u32 *filter = NULL;             // annhip_index_set_filter: the index's copy of the allow list, u32[ceil(n / 32)] (NULL = none)
   long long filter_count = -1;    // allowed rows among [0, n), taken when the filter was set (-1 = no filter)
   u32 *tags = NULL;               // annhip_index_set_tags: the index's copy of the rows' tag words, u32[n] (NULL = none)
@@ -589,7 +600,102 @@ static void drop_half_rows(annhip_index *ix) {
   if (ix->d_points_h) HIPCHECK(hipFree(ix->d_points_h));
   ix->d_points_h = NULL;
   ix->rows = ANNHIP_ROWS_NATIVE;
+  ix->prune_ready = false;
 }
+
+// ----------------------------------------------------------------------------- pruned stage 1 (annhip_index_set_prune)
+// Contract: include/ann_hip.h.  Kernels: ann_prune_kernels.h.  The narrow copy is the one annhip_index_set_rows makes.
+static int layout_code(size_t d, bool allow_oc);  // (the layout table, below)
+static bool layout_is_generic(int code);
+static int prune_keys(size_t k) {
+  const int K1 = (int)k + 1;
+  // measured at cfg3 (k = 10), ms per step with 16 / 24 / 32 keys: 0.943 / 1.025 / 1.125 against 1.245 native -- the narrow
+  // gather is bound by its selection, not by bytes, and every query was certified at all three
+  int kp = env().prune_k > 0 ? env().prune_k : std::max(16, 3 * K1 / 2);
+  return std::min(ANN_PRUNE_KMAX, std::max(kp, K1));
+}
+// what keeps this index from pruning whatever the query (NULL: nothing)
+static const char *prune_refusal(const annhip_index *ix) {
+#ifndef USE_FLOAT
+  return "pruning is a feature of the f32 library only";
+#else
+  return (ix->lo != 0 || ix->hi != ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+         : ix->tail_m                     ? "the index has appended rows (annhip_index_drop_tail, or Index.compact)"
+         : ix->k + 1 > 32                 ? "k + 1 must be at most 32"
+         : layout_is_generic(layout_code(ix->d, true)) ? "no register layout for this row length"
+                                          : NULL;
+#endif
+}
+// queries of this index take the pruned stage 1 right now (parity mode, native rows selected, nothing appended)
+static bool prune_active(const annhip_index *ix) {
+  return ix->prune_ready && ix->d_points_h && !ix->fixed && ix->rows == ANNHIP_ROWS_NATIVE && !ix->tail_m && ix->lo == 0 &&
+         ix->hi == ix->n;
+}
+// Apply `mode` to the index: the narrow copy and E are made here, never inside a query call (synchronous, null stream).
+// Returns -1 -- with one line on stderr where `who` is given -- and changes nothing where mode 1 cannot be served.
+static int prune_setup(annhip_index *ix, int mode, const char *who) {
+  RandGuard keep_callers_stream;
+  if (mode == 0) {
+    ix->prune = 0, ix->prune_ready = false;  // the copy stays: annhip_index_set_rows shares it
+    return 0;
+  }
+  const char *why = prune_refusal(ix);
+  const int kp = prune_keys(ix->k);
+  const size_t count = ix->n * ix->d;
+  if (!why && mode < 0) {  // auto: small indexes keep the native path
+    size_t free_b = 0, total_b = 0;
+    if ((size_t)ix->P1 < 8 * (size_t)kp) why = "candidate rows too short";
+    else if (count * sizeof(FT) < ((size_t)1 << 30)) why = "native rows below 1 GiB";
+    else if (!ix->d_points_h &&
+             (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < count * sizeof(RN) + ((size_t)2 << 30)))
+      why = "not enough free device memory for the narrow copy";
+  }
+  bool made = false;
+  double E = 0;
+  if (!why) {
+    HIPCHECK(hipDeviceSynchronize());  // the native rows may have been written on another stream
+    if (!ix->d_points_h) {
+      ix->d_points_h = dev_alloc<RN>(count);
+      rows_to_narrow(count, ix->d_points, ix->d_points_h);
+      HIPCHECK(hipGetLastError());
+      made = true;
+    }
+    unsigned long long *acc = dev_alloc<unsigned long long>(2), host[2] = {0, 0};
+    HIPCHECK(hipMemset(acc, 0, sizeof host));
+    prune_rowerr_kernel<<<grid_for((ix->n + 3) / 4, 1, 8192), 256>>>(ix->n, (int)ix->d, ix->d_points, ix->d_points_h, acc);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(host, acc, sizeof host, hipMemcpyDeviceToHost));
+    HIPCHECK(hipFree(acc));
+    double worst;
+    memcpy(&worst, &host[0], sizeof worst);
+    E = sqrt(worst) * (1.0 + 0x1p-20);  // rounded up: the double sum of d squares is within d 2^-53 of the real one
+    if (host[1] || !(E < std::numeric_limits<double>::infinity())) {
+      why = "a row does not survive " ANN_NARROW_WHAT " (overflow or NaN): no finite error bound";
+      if (made) {
+        HIPCHECK(hipFree(ix->d_points_h));
+        ix->d_points_h = NULL;
+      }
+    }
+  }
+  if (why) {
+    if (mode == 1) {
+      if (who) fprintf(stderr, "%s: %s\n", who, why);
+      return -1;
+    }
+    ix->prune = mode, ix->prune_ready = false;  // auto: stays off, silently
+    return 0;
+  }
+  ix->prune = mode, ix->prune_ready = true, ix->prune_E = E, ix->prune_kp = kp;
+  return 0;
+}
+extern "C" int annhip_index_set_prune(annhip_index *ix, int mode) {
+  if (mode < -1 || mode > 1) {
+    fprintf(stderr, "annhip_index_set_prune: unknown mode %d (-1 auto, 0 off, 1 on where eligible)\n", mode);
+    return -1;
+  }
+  return prune_setup(ix, mode, "annhip_index_set_prune");
+}
+extern "C" int annhip_index_prune(const annhip_index *ix) { return prune_active(ix) ? 1 : 0; }
 
 // ----------------------------------------------------------------------------- appended rows (the tail)
 // Contract: include/ann_hip.h.  Kernels: ann_tail_kernels.h.  All of it synchronous on the null stream.
@@ -651,6 +757,7 @@ extern "C" int annhip_index_append(annhip_index *ix, const ftype *rows, int rows
   }
   if (!count) return 0;
   HIPCHECK(hipDeviceSynchronize());
+  if (ix->prune_ready) drop_half_rows(ix);  // a pruned stage 1 never sees a tail: its copy and bound go (rows are native here)
   tail_grow(ix, ix->tail_m + count);
   const size_t at = n_total(ix);
   HIPCHECK(hipMemcpy(ix->d_tail + ix->tail_m * ix->d, rows, sizeof(FT) * count * ix->d,
@@ -743,6 +850,7 @@ extern "C" annhip_index *annhip_index_create(const save_t *save, const ftype *po
   HIPCHECK(hipMemcpy(ix->d_bases, save->bases, sizeof(FT) * ix->T * ix->ds * ix->d, hipMemcpyHostToDevice));
   build_segments(ix);
   finish_geometry(ix);
+  (void)prune_setup(ix, env().prune, "ANN_HIP_PRUNE=1");
   return ix;
 }
 
@@ -1020,15 +1128,39 @@ __global__ void sum_u32_kernel(size_t count, const u32 *__restrict__ v, unsigned
   if (lane_id() == 0) atomicAdd(out, acc);
 }
 
+// the HIP-event pair around one stage-1 "launch" of a profiled index (s1_prof_end: and the gathered-row statistics)
+static EventPair s1_prof_begin(annhip_index *ix, hipStream_t s) {
+  EventPair ev;
+  if (ix->ev_free.empty()) {
+    HIPCHECK(hipEventCreate(&ev.a));
+    HIPCHECK(hipEventCreate(&ev.b));
+  } else {
+    ev = ix->ev_free.back();
+    ix->ev_free.pop_back();
+  }
+  HIPCHECK(hipEventRecord(ev.a, s));
+  return ev;
+}
+static void s1_prof_end(annhip_index *ix, EventPair ev, size_t Q, const u32 *nvo, hipStream_t s) {
+  HIPCHECK(hipEventRecord(ev.b, s));
+  ix->ev_used.push_back(ev);
+  // gathered-row statistics only while measuring: one small reduction kernel, outside the event bracket
+  if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
+}
+
 static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias,
                           const u32 *codes, FT *cand_d, u32 *cand_i, u32 *nvt, u32 *nvo, hipStream_t s,
                           const std::vector<TryInfo> &h_tries, int use_seg, FusedTail F = FusedTail{0, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL},
-                          Key *cand_key = NULL, int pieces = 1, int slots = 0, size_t qstride = 0) {
+                          Key *cand_key = NULL, int pieces = 1, int slots = 0, size_t qstride = 0, int keys = 0,
+                          bool bracket = true) {
   // qstride: stride of the try-major code array the kernel reads as codes[try * qstride + x] (0 = Q; a host that answers
   // a SLICE of a larger batch passes the whole batch's size and a code pointer offset to the slice, annhip_query_slice)
+  // keys: distinct keys selected per query (0 = k + 1; the pruned stage 1 preselects more, F.enabled == 0 only)
+  // bracket: false = the caller brackets this launch together with what follows it (s1_prof_begin / s1_prof_end)
   const int kq = (int)(qstride ? qstride : Q);
   if (!Q) return;
-  const int K1 = P.k + 1, W = stage1_waves(P.P1, (double)(P.hi - P.lo) / (double)P.n), cap = stage1_cap(W, K1);
+  if (keys && F.enabled) die("launch_stage1: a preselection has no fused tail");
+  const int K1 = keys ? keys : P.k + 1, W = stage1_waves(P.P1, (double)(P.hi - P.lo) / (double)P.n), cap = stage1_cap(W, K1);
   const size_t smem = stage1_lds_bytes(P, W, K1, cap, F.enabled == 1 ? F.len2 : 0);
   u32 runs_used = 0;  // (try, hamming neighbour) runs that start below P1, in slot order
   for (int t = 0; t < P.T; t++)
@@ -1042,17 +1174,8 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   unsigned max_grid = 0xFFFFFFFFu;
   if (slots > 0) max_grid = std::max(1u, (unsigned)device_cus() * 4u * (unsigned)slots / (unsigned)W);
   EventPair ev;
-  const bool prof = ix && ix->profile;
-  if (prof) {
-    if (ix->ev_free.empty()) {
-      HIPCHECK(hipEventCreate(&ev.a));
-      HIPCHECK(hipEventCreate(&ev.b));
-    } else {
-      ev = ix->ev_free.back();
-      ix->ev_free.pop_back();
-    }
-    HIPCHECK(hipEventRecord(ev.a, s));
-  }
+  const bool prof = ix && ix->profile && bracket;
+  if (prof) ev = s1_prof_begin(ix, s);
   // (Chaining the stage-1 launches of overlapping batches through an event was tried and is slower, 7.9 vs 8.3 M q/s:
   // letting consecutive gathers overlap is what hides the workgroup tail of each launch.)
   const size_t np = (size_t)std::max(1, std::min(pieces, 64)), per = (Q + np - 1) / np;
@@ -1078,14 +1201,34 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
     });
   });
   HIPCHECK(hipGetLastError());
-  if (prof) {
-    HIPCHECK(hipEventRecord(ev.b, s));
-    ix->ev_used.push_back(ev);
-    // gathered-row statistics only while measuring: one small reduction kernel, outside the event bracket
-    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
-  }
+  if (prof) s1_prof_end(ix, ev, Q, nvo, s);
   if (ix) ix->s1_launches += 1;
 }
+
+#ifdef USE_FLOAT
+// The second half of the pruned stage 1 (ann_prune_kernels.h): rescore the kp preselected candidates of every query on
+// the native rows, certify, apply finalize1's test.  P: the native-row parameters.
+static void launch_prune_rescore(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int kp, const FT *pre_d,
+                                 const u32 *pre_i, const u32 *nvt, u32 *nvo, u32 *top_i, FT *top_d, u32 *fl, u32 *d_fcount,
+                                 hipStream_t s) {
+  if (!Q) return;
+  if (kp < P.k + 1 || kp > ANN_PRUNE_KMAX || P.k + 1 > 32) die("launch_prune_rescore: preselection size out of range");
+  PruneArgs A = {};
+  A.points = P.points, A.y = y, A.pre_d = pre_d, A.pre_i = pre_i, A.nv_tot = nvt, A.nv_own = nvo;
+  A.top_id = top_i, A.top_dist = top_d, A.flist = fl, A.fcount = d_fcount;
+  A.exact_total = ix->d_rows + 2, A.uncertified = ix->d_rows + 4;
+  A.E = ix->prune_E;
+  A.n = P.n, A.Q = (u32)Q, A.L1 = P.L1, A.P1 = P.P1;
+  A.d = P.d, A.k = P.k, A.Kp = kp;
+  const dim3 grid((unsigned)((Q + ANN_PRUNE_WAVES - 1) / ANN_PRUNE_WAVES)), block(64 * ANN_PRUNE_WAVES);
+  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D != 0 && !OcCode<D>::GEN) hipLaunchKernelGGL(prune_rescore_kernel<D>, grid, block, 0, s, A);
+    else die("launch_prune_rescore: no register layout for this row length");
+  });
+  HIPCHECK(hipGetLastError());
+}
+#endif
 
 // ---- fixed mode with pair bits (annhip_index_set_probe; ann_probe_kernels.h)
 // The hash kernels with the ranking: launch_codes' three forms, every query hashed; pbits u8[Q][T][pb].
@@ -1468,7 +1611,11 @@ static long finalize_and_fallback(annhip_index *ix, const QParams &P, size_t Q, 
                                   unsigned long long *exact_total, bool device_driven, hipStream_t s, size_t qstride = 0,
                                   bool prefinalized = false) {
   // prefinalized: stage 1 applied finalize1's test itself (FusedTail.enabled == 2): flist / *d_fcount / top_* are set
+  // cand_d == NULL (with prefinalized; the pruned stage 1, whose uncertified queries have no exact candidate list): the
+  // tie path derives the list from the row, as the staged API does
   const int K1 = P.k + 1;
+  unsigned long long *tie_ctr = ix ? ix->d_rows + 3 : NULL;
+  const TieArgs tie0 = cand_d ? TieArgs{cand_d, cand_i, K1, tie_ctr, 0} : TieArgs{NULL, NULL, K1, tie_ctr, 1};
   u32 nflag = 0;
   u32 *fl = (u32 *)flist.need(sizeof(u32) * Q);
   const size_t row_bytes = (size_t)P.Lc1 * (sizeof(FT) + sizeof(u32));
@@ -1494,7 +1641,7 @@ static long finalize_and_fallback(annhip_index *ix, const QParams &P, size_t Q, 
         launch_rows<MODE_TABLE>(P, Q, y, alias, codes, fl + p0, 0, nq, P.Lc1, NULL, NULL, ids, dist, rows_done, s, d_fcount,
                                 (u32)p0, qstride);
         launch_exact_select(P.L1, P.Lc1, P.Lc1, P.k, nq, ids, dist, fl + p0, 0, top_i, top_d, ostride, ooff, s, d_fcount,
-                            NULL, 1024, (u32)p0, TieArgs{cand_d, cand_i, K1, ix ? ix->d_rows + 3 : NULL, 0});
+                            NULL, 1024, (u32)p0, tie0);
       }
       return -1;
     }
@@ -1518,7 +1665,7 @@ static long finalize_and_fallback(annhip_index *ix, const QParams &P, size_t Q, 
     const u32 *qidx = mode == 0 ? fl + q0 : NULL;
     launch_rows<MODE_TABLE>(P, Q, y, alias, codes, qidx, (u32)q0, nq, P.Lc1, NULL, NULL, ids, dist, rows_done, s, NULL, 0, qstride);
     launch_exact_select(P.L1, P.Lc1, P.Lc1, P.k, nq, ids, dist, qidx, (u32)q0, top_i, top_d, ostride, ooff, s, NULL, NULL, 1024,
-                        0, mode == 0 ? TieArgs{cand_d, cand_i, K1, ix ? ix->d_rows + 3 : NULL, 0} : TieArgs{NULL, NULL, 0, NULL, 0});
+                        0, mode == 0 ? tie0 : TieArgs{NULL, NULL, 0, NULL, 0});
   }
   return (long)nflag;
 }
@@ -1635,6 +1782,12 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     ix->queries += (double)Q;
     return 0;
   }
+  // pruned stage 1 (annhip_index_set_prune): preselect on the narrow copy, rescore on native rows -- the same answers
+#ifdef USE_FLOAT
+  const bool pruned = mode == 0 && !codes_ext && prune_active(ix) && K1 <= 32 && ix->prune_kp >= K1;
+#else
+  const bool pruned = false;
+#endif
   // ---- fused path: stage 2 runs in the tail of every query's stage-1 workgroup; only rejected queries come back
   {
     const size_t xrow = (size_t)P.Lc1 * (sizeof(FT) + sizeof(u32));
@@ -1642,7 +1795,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     // Measured: +5 % at Q = 1k (launch-bound), neutral at cfg3 (Q = 10k, d = 128), -6 % at Q = 10k, d = 64 -- the tail
     // keeps the workgroup's registers/LDS occupied through a chain of dependent loads.  So: small batches only.
     const bool want = !codes_ext && (env().fuse >= 0 ? env().fuse != 0 : Q <= 2048);  // ANN_HIP_FUSE: 0 = never, 1 = whenever possible
-    if (mode == 0 && whole && want && P.Lc2 <= 1024 && Q * xrow <= env().exact_bytes) {
+    if (mode == 0 && whole && want && !pruned && P.Lc2 <= 1024 && Q * xrow <= env().exact_bytes) {
       FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * k);
       u32 *fl = (u32 *)ws.flist.need(sizeof(u32) * Q);
       u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
@@ -1673,6 +1826,28 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     }
   }
   bool prefinalized = false;
+#ifdef USE_FLOAT
+  if (pruned) {
+    const int kp = ix->prune_kp;
+    FT *pre_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * kp);
+    u32 *pre_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * kp);
+    nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
+    u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
+    u32 *fl = (u32 *)ws.flist.need(sizeof(u32) * Q);
+    prefinalized = true;
+    if (!fcount_zeroed) zero_u32_kernel<<<1, 1, 0, s>>>(ws.d_fcount);
+    QParams Pn = P;
+    Pn.points_h = ix->d_points_h;
+    // one stage-1 "launch" for the statistics: the event pair brackets preselection and rescoring together
+    EventPair ev;
+    if (ix->profile) ev = s1_prof_begin(ix, s);
+    launch_stage1(ix, Pn, Q, y, alias, codes, pre_d, pre_i, nvt, nvo, s, ix->h_tries, ix->use_seg,
+                  FusedTail{0, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL}, NULL, 1, env().s1_slots, qstride, kp, false);
+    launch_prune_rescore(ix, P, Q, y, kp, pre_d, pre_i, nvt, nvo, top_i, top_d, fl, ws.d_fcount, s);
+    if (ix->profile) s1_prof_end(ix, ev, Q, nvo, s);
+    // cand_d / cand_i stay NULL: the exact path of a flagged query derives its own list
+  } else
+#endif
   if (mode == 0) {
     cand_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * K1);
     cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
@@ -2431,7 +2606,8 @@ extern "C" void annhip_stats(annhip_index *ix, double out[8], int reset) {
   unsigned long long other = 0;
   for (int i = 0; i < 64; i++) other += rows[8 + i * 8];
   out[0] = ix->s1_launches, out[1] = ix->s1_ms, out[2] = (double)rows[0], out[3] = (double)other;
-  out[4] = (double)rows[2], out[5] = ix->queries, out[6] = (double)rows[3] /* answered by the tie path */, out[7] = 0;
+  out[4] = (double)rows[2], out[5] = ix->queries, out[6] = (double)rows[3] /* answered by the tie path */;
+  out[7] = (double)rows[4] /* pruned stage 1: not certified */;
   if (reset) {
     ix->s1_launches = ix->s1_ms = ix->queries = 0;
     for (double &v : ix->seg_ms) v = 0;
@@ -3410,6 +3586,7 @@ extern "C" annhip_index *annhip_precomp_finish(annhip_precomp *h, const uint32_t
   HIPCHECK(hipFree(h->d_bad));
   HIPCHECK(hipFree(h->solo));
   delete h;
+  (void)prune_setup(ix, env().prune, "ANN_HIP_PRUNE=1");
   return ix;
 }
 

@@ -239,6 +239,26 @@ int annhip_index_copy_words(const annhip_index *ix, int what, uint32_t *dst_dev)
 #define ANNHIP_ROWS_F32 2
 int annhip_index_set_rows(annhip_index *ix, int rows);
 int annhip_index_rows(const annhip_index *ix);
+/* Pruned stage 1 of the parity path (f32 library; csrc/ann_prune_kernels.h): the SAME ids and distance bits for fewer
+ * bytes.  Stage 1 preselects K' > k + 1 keys per query on the binary16 copy of the rows (the copy annhip_index_set_rows
+ * makes), rescores those K' candidates on the native rows with the query path's distance tree, and tests per query
+ * whether the k + 1 smallest exact keys are provably the ones native stage 1 selects among all candidates (the
+ * preselection left nothing out, or every candidate it left out lies above the (k+1)-th exact distance by a bound built
+ * from E = max over the rows of ||p - binary16(p)||_2).  A query that cannot be certified takes the exact path that
+ * flagged queries take; stage 2 reads native rows.  K' = max(16, 3 (k + 1) / 2), at most 64.
+ * mode: 0 off; 1 on where eligible; -1 auto (the default of a new index; ANN_HIP_PRUNE sets another one): on where
+ * eligible AND the index is large enough to gain (P1 >= 8 K', native rows of 1 GiB or more, free device memory for the
+ * copy).  Eligible: f32 library, rows [0, n) on this device, no appended rows, k + 1 <= 32, a row length with a register
+ * layout, and E finite (no row overflows binary16).  The copy (n*d*2 bytes) and E are made by this call -- or when the
+ * index is created / precomp finishes, under the auto rule -- never by a query; reshard, append and destroy drop them.
+ * A query is pruned only in parity mode with native rows selected: fixed mode, annhip_index_set_rows(F16) (which keeps
+ * meaning what it says), annhip_query_slice and mode = 1 queries take their usual path.  Returns 0, or -1 with one line
+ * on stderr and nothing changed where mode 1 cannot be served (always in the f64 library) or mode is unknown.
+ * annhip_index_prune() = 1 while annhip_query / annhip_query_on on this index are pruned, else 0.
+ * Statistics: annhip_stats out[7] counts the uncertified queries; out[2] counts native-row equivalents of the bytes
+ * requested (narrow rows / 2 + rescored rows); the stage-1 event pair brackets preselection and rescoring together. */
+int annhip_index_set_prune(annhip_index *ix, int mode);
+int annhip_index_prune(const annhip_index *ix);
 /* Point-shard an index that was built from all n rows: from now on this device owns rows [row_lo,row_hi) only
  * and reads them from shard_points_dev (device pointer to those rows, borrowed).  Tables and graph stay. */
 void annhip_index_reshard(annhip_index *ix, const ftype *shard_points_dev, size_t row_lo, size_t row_hi);
@@ -624,7 +644,8 @@ void annhip_profile(annhip_index *ix, int profile);
 /* out[0]=stage-1 launches, out[1]=their total ms (events; only while profiling), out[2]=rows gathered in stage 1
  * (owned valid slots; only with profile = 1), out[3]=rows gathered in stage-2/exact rows kernels (only with profile =
  * 1), out[4]=queries flagged for the exact path, out[5]=queries seen, out[6]=of the flagged ones: answered by the tie
- * path (ann_tie.h) instead of the literal network; counters accumulate since the last reset (reset != 0 clears them
+ * path (ann_tie.h) instead of the literal network, out[7]=queries a pruned stage 1 could not certify (they are among
+ * out[4]); counters accumulate since the last reset (reset != 0 clears them
  * after reading). */
 void annhip_stats(annhip_index *ix, double out[8], int reset);
 /* While profiling, annhip_query also drops HIP events at its stage boundaries; out[0..5] = accumulated ms of

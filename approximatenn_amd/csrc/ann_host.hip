@@ -609,8 +609,8 @@ static int layout_code(size_t d, bool allow_oc);  // (the layout table, below)
 static bool layout_is_generic(int code);
 static int prune_keys(size_t k) {
   const int K1 = (int)k + 1;
-  // measured at cfg3 (k = 10), ms per step with 16 / 24 / 32 keys: 0.943 / 1.025 / 1.125 against 1.245 native -- the narrow
-  // gather is bound by its selection, not by bytes, and every query was certified at all three
+  // measured at cfg3 (k = 10), ms per step with 16 / 24 / 32 keys: 0.859 / 0.878 / 0.894 against 1.245 native (0.943 / 1.025 /
+  // 1.125 while the selection ran through an LDS buffer); every query was certified at all three, so more keys buy nothing
   int kp = env().prune_k > 0 ? env().prune_k : std::max(16, 3 * K1 / 2);
   return std::min(ANN_PRUNE_KMAX, std::max(kp, K1));
 }
@@ -1104,8 +1104,10 @@ static int stage1_cap(int W, int K1) {
   if (cap < K1 + 128) cap = K1 + 128;
   return (cap + 63) & ~63;
 }
-static size_t stage1_lds_bytes(const QParams &P, int W, int K1, int cap, u32 tail_len = 0) {
-  size_t b = sizeof(Key) * (size_t)W * cap + 2 * sizeof(Key) * (size_t)W * K1 + sizeof(TryInfo) * (size_t)P.T +
+// regs: stage1_select_kernel<..., REGS = true> -- no candidate buffers, one kout (wave 0's)
+static size_t stage1_lds_bytes(const QParams &P, int W, int K1, int cap, u32 tail_len = 0, bool regs = false) {
+  size_t b = sizeof(Key) * (regs ? 0 : (size_t)W * cap) + sizeof(Key) * (size_t)(regs ? 1 : W) * K1 +
+             sizeof(Key) * (size_t)W * K1 + sizeof(TryInfo) * (size_t)P.T +
              sizeof(u32 *) * (size_t)W * ANN_WAVE + sizeof(u32) * (size_t)W * ANN_S1_CHUNK +
              sizeof(u32) * (size_t)W * ANN_WAVE + sizeof(u32) * (size_t)P.T + sizeof(int) * (size_t)W + sizeof(u32) * 4 +
              3 * sizeof(u32) * (size_t)tail_len;
@@ -1161,7 +1163,9 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   if (!Q) return;
   if (keys && F.enabled) die("launch_stage1: a preselection has no fused tail");
   const int K1 = keys ? keys : P.k + 1, W = stage1_waves(P.P1, (double)(P.hi - P.lo) / (double)P.n), cap = stage1_cap(W, K1);
-  const size_t smem = stage1_lds_bytes(P, W, K1, cap, F.enabled == 1 ? F.len2 : 0);
+  // the running selection in registers where the layout's gather offers keys by ballot and the list fits two registers
+  const bool regs = K1 <= ANN_SEL_REGS_KMAX && sel_regs_code(layout_code(P.d));
+  const size_t smem = stage1_lds_bytes(P, W, K1, cap, F.enabled == 1 ? F.len2 : 0, regs);
   u32 runs_used = 0;  // (try, hamming neighbour) runs that start below P1, in slot order
   for (int t = 0; t < P.T; t++)
     for (int yy = 0; yy <= P.ds; yy++)
@@ -1181,17 +1185,25 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
   const size_t np = (size_t)std::max(1, std::min(pieces, 64)), per = (Q + np - 1) / np;
   with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
     with_rows(P, [&](auto rt) {
-      auto launch = [&](auto sg, auto fu) {
+      auto launch_sel = [&](auto sg, auto fu, auto rg) {
         constexpr int D = decltype(dd)::value, SG = decltype(sg)::value;
-        constexpr bool FU = decltype(fu)::value;
+        constexpr bool FU = decltype(fu)::value, RG = decltype(rg)::value;
         using RT = typename decltype(rt)::type;
-        allow_lds(stage1_select_kernel<D, SG, FU, RT>, smem);
+        allow_lds(stage1_select_kernel<D, SG, FU, RT, RG>, smem);
         for (size_t a = 0; a < Q; a += per) {
           QParams Pp = P;
           Pp.q0 = (u32)a, Pp.qn = (u32)std::min(per, Q - a);
-          hipLaunchKernelGGL((stage1_select_kernel<D, SG, FU, RT>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem,
+          hipLaunchKernelGGL((stage1_select_kernel<D, SG, FU, RT, RG>), dim3(std::min<unsigned>(Pp.qn, max_grid)), dim3(64 * W), smem,
                              s, Pp, kq, y, alias, codes, K1, cap, runs_used, cand_d, cand_i, nvt, nvo, F, cand_key);
         }
+      };
+      auto launch = [&](auto sg, auto fu) {
+        if constexpr (sel_regs_layout<decltype(dd)::value>()) {
+          if (regs) return launch_sel(sg, fu, std::true_type{});
+        } else if (regs) {
+          die("launch_stage1: register selection chosen for a layout without one");
+        }
+        launch_sel(sg, fu, std::false_type{});
       };
       if (use_seg == 2) launch(Int<2>{}, std::false_type{});
       else if (use_seg && F.enabled == 1) launch(Int<1>{}, std::true_type{});
@@ -2358,6 +2370,28 @@ extern "C" void annhip_test_sort_rows(size_t L, size_t k, size_t nq, uint32_t *i
                       TieArgs{reinterpret_cast<const FT *>(cand_d_dev), cand_i_dev, (int)k + 1, resolved_dev,
                               cand_d_dev ? 0 : derive});
   HIPCHECK(hipStreamSynchronize(NULL));
+}
+
+// Test hook: stage 1's running selection (test_select_kernel) on ns key streams, stream b = entries [off[b], off[b+1]).
+extern "C" int annhip_test_select(size_t ns, const uint32_t *off_dev, const ftype *dist_dev, const uint32_t *id_dev, size_t K1,
+                                  int W, int lds, ftype *out_dist_dev, uint32_t *out_id_dev) {
+  gpu_init();
+  if (K1 < 1 || K1 > 256 || W < 1 || W > 4 || (!lds && K1 > ANN_SEL_REGS_KMAX)) return -1;
+  if (!ns) return 0;
+  const int cap = stage1_cap(W, (int)K1);
+  const size_t smem = sizeof(Key) * (lds ? (size_t)W * cap : 0) + sizeof(Key) * (size_t)(lds ? W : 1) * K1 +
+                      sizeof(Key) * (size_t)W * K1 + sizeof(int) * (size_t)W;
+  auto launch = [&](auto rg) {
+    constexpr bool RG = decltype(rg)::value;
+    allow_lds(test_select_kernel<RG>, smem);
+    hipLaunchKernelGGL(test_select_kernel<RG>, dim3((unsigned)ns), dim3(64 * W), smem, NULL, off_dev,
+                       reinterpret_cast<const FT *>(dist_dev), id_dev, (int)K1, cap, reinterpret_cast<FT *>(out_dist_dev), out_id_dev);
+  };
+  if (lds) launch(std::false_type{});
+  else launch(std::true_type{});
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(NULL));
+  return 0;
 }
 
 // A HIP stream whose kernels may use every compute unit except `reserve` of them (the highest-numbered ones).

@@ -64,6 +64,9 @@ struct QParams {
 #ifndef ANN_S1_PREFETCH
 #define ANN_S1_PREFETCH 3  // row passes per wave kept in flight + 1 (gather_select)
 #endif
+#ifndef ANN_S1_PREFETCH_NARROW
+#define ANN_S1_PREFETCH_NARROW 3  // the same for narrow rows (RT = RN) in the power-of-two layouts, where a pass is half the bytes; cfg3 pruned, ms per step, three alternating runs each, 2 / 3 / 4: 0.852-0.865 / 0.848-0.861 / 0.901-0.906
+#endif
 #ifndef ANN_S1_PREFETCH_OC
 #define ANN_S1_PREFETCH_OC 2  // the same for the oc-lanes-per-row layouts (d = 80, 96, 160 ...): d = 80 measured 2 / 3 / 4: 69.8 / 66.1 / 63 % of peak (124 / 143 VGPRs)
 #endif
@@ -384,6 +387,110 @@ __device__ __forceinline__ void sel_shrink(SelState &S) {
   wave_lds_sync();
 }
 
+// The same selection with the list in registers (ann_device.h, wave-resident top-K): lane i of `lo` holds the i-th
+// smallest distinct key seen so far, of `hi` the (64+i)-th (K1 <= 128; `hi` stays untouched while K1 <= 64), and tau is
+// the exact K1-th smallest after every insert.  No candidate buffer, no shrink, and the wave's final selection is free:
+// the list is already sorted.  stage1_select_kernel's state wherever the layout's gather takes it (sel_regs_layout) and
+// K1 fits; the LDS form above serves everything else.
+struct SelRegs {
+  Key lo, hi;
+  int K1;
+  Key tau;
+};
+// the layouts whose gather offers keys by ballot, RPW rows per pass: LPR lanes per row and the oc-lanes-per-row ring
+// (by layout code for the host, by template argument for the kernels)
+constexpr bool sel_regs_code(int code) {
+  return code > 0 || (code < 0 && code != ANN_D_FOLD2 && code != ANN_D_FOLD3 && code != ANN_D_FOLD4 && code != ANN_D_FOLD4G &&
+                      code != ANN_D_FOLD5G);
+}
+template <int D>
+constexpr bool sel_regs_layout() {
+  static_assert(sel_regs_code(D) == (D > 0 || (D < 0 && !OcCode<D>::GEN && OcCode<D>::FOLD == 0)), "the two forms of the rule differ");
+  return sel_regs_code(D);
+}
+#define ANN_SEL_REGS_KMAX (2 * ANN_WAVE)
+template <bool REGS>
+struct SelOf {
+  typedef SelState T;
+};
+template <>
+struct SelOf<true> {
+  typedef SelRegs T;
+};
+
+// One gather pass: the lanes with `pass` set (key < tau tested by the caller, vector-side) hand their keys to the selection.
+// rpw: the most keys a pass can bring (the LDS form keeps that much room).
+__device__ __forceinline__ void sel_offer(SelState &S, Key key, bool pass, int rpw) {
+  const u64 mm = __ballot(pass);
+  if (mm) {
+    if (pass) S.kbuf[S.kcnt + mask_rank(mm)] = key;
+    S.kcnt += __popcll(mm);
+    if (S.kcnt + rpw > S.cap) sel_shrink(S);
+  }
+}
+__device__ __forceinline__ void sel_offer(SelRegs &S, Key key, bool pass, int) {
+  const u64 mm = __ballot(pass);
+  if (mm) {
+    if (S.K1 <= ANN_WAVE) wave_topk_offer(S.lo, S.tau, key, mm, S.K1);  // wave-uniform
+    else wave_topk_offer2(S.lo, S.hi, S.tau, key, mm, S.K1);
+  }
+}
+
+__device__ __forceinline__ void sel_init(SelState &S, Key *kbuf, Key *kout, int K1, int cap) {
+  S.kbuf = kbuf, S.kout = kout;
+  S.kcnt = 0, S.K1 = K1, S.cap = cap, S.tau = key_max();
+}
+__device__ __forceinline__ void sel_init(SelRegs &S, Key *, Key *, int K1, int) {
+  S.lo = S.hi = S.tau = key_max();
+  S.K1 = K1;
+}
+
+// The calling wave's up-to-K1 smallest distinct keys, ascending, to out[0..m) (LDS); returns m.
+__device__ __forceinline__ int sel_wave_result(SelState &S, Key *out) {
+  const int m = wave_select_smallest(S.kbuf, S.kcnt, S.K1, S.kout);
+  for (int i = lane_id(); i < m; i += ANN_WAVE) out[i] = S.kout[i];
+  return m;
+}
+__device__ __forceinline__ int sel_wave_result(SelRegs &S, Key *out) {
+  // listed keys fill the lanes from 0 upwards; what an insert pushed beyond rank K1 - 1 is still there and is not wanted
+  int m = __popcll(__ballot(!key_eq(S.lo, key_max())));
+  if (S.K1 > ANN_WAVE) m += __popcll(__ballot(!key_eq(S.hi, key_max())));
+  m = min(m, S.K1);
+  const int lane = lane_id();
+  if (lane < m) out[lane] = S.lo;
+  if (ANN_WAVE + lane < m) out[ANN_WAVE + lane] = S.hi;
+  return m;
+}
+
+// Wave 0 only, after the workgroup's barrier: the K1 smallest distinct keys of the W waves' results (mbuf[ww * K1 + i],
+// i < mcnt[ww]; duplicates ACROSS waves occur -- the same id reached through runs of different waves) to kout[0..m) (LDS,
+// visible to the whole wave on return); returns m.  S: wave 0's own state.
+__device__ __forceinline__ int sel_merge(SelState &S, const Key *mbuf, const int *mcnt, int W, Key *kout) {
+  const int lane = lane_id();
+  int total = 0;
+  for (int ww = 0; ww < W; ww++) {  // cap >= W*K1 (host guarantees)
+    const int m = mcnt[ww];
+    for (int i = lane; i < m; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * S.K1 + i];
+    total += m;
+  }
+  wave_lds_sync();
+  return wave_select_smallest(S.kbuf, total, S.K1, kout);  // (kout is S.kout)
+}
+__device__ __forceinline__ int sel_merge(SelRegs &S, const Key *mbuf, const int *mcnt, int W, Key *kout) {
+  const int lane = lane_id();
+  for (int ww = 1; ww < W; ww++) {  // the other waves' keys are offered to wave 0's list, which still holds its own
+    const int mw = mcnt[ww];
+    for (int base = 0; base < mw; base += ANN_WAVE) {
+      const bool in = base + lane < mw;
+      const Key key = in ? mbuf[(size_t)ww * S.K1 + base + lane] : key_max();
+      sel_offer(S, key, in && key_less(key, S.tau), 0);
+    }
+  }
+  const int m = sel_wave_result(S, kout);
+  wave_lds_sync();
+  return m;
+}
+
 // ---- folded layout for row lengths that are not a power of two (d = 100, 200, 384, 768, 33, 77 ...).
 // The literal tree (compute.cl:160-167) halves s = d, d>>1, ... and at each level adds m[z + h] (and, into z = 0, the
 // left-over m[s-1] of an odd s) to m[z].  Its first L levels are folded INTO a lane: lane z < s_L of a row's lane group
@@ -510,10 +617,11 @@ __device__ __forceinline__ void gather_fold(const QParams &P, const FoldPlan &fp
 
 // B) gather the rows listed in list[0..cnt) (LDS), squared L2 to the query in the reference's tree order, keep
 // the keys that can still matter.  D > 0: LPR lanes per row, the next pass is prefetched while this one is reduced.
-template <int D, typename RT = FT>
+// ST: the selection's state, SelState (LDS buffer) or -- these two layouts only -- SelRegs (register list).
+template <int D, typename RT = FT, typename ST = SelState>
 __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list, int cnt, int alias, u32 x,
                                               const VT (&a)[RowChunks<D>::C],
-                                              const FT *yq, FT *scratch, SelState &S, const FT *yrow = NULL) {
+                                              const FT *yq, FT *scratch, ST &S, const FT *yrow = NULL) {
   const int lane = lane_id();
   const RT *rows = q_rows<RT>(P);
   typedef typename RowRaw<RT>::T RR;
@@ -522,7 +630,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
     // (each pass = RPW rows = 64 lanes x C x 16 B).  The loop is unrolled by PF so that every buffer has a fixed
     // register home; a buffer is re-loaded right after it has been reduced.
     typedef RowLay<D> L;
-    constexpr int PF = ANN_S1_PREFETCH;
+    constexpr int PF = std::is_same<RT, FT>::value ? ANN_S1_PREFETCH : ANN_S1_PREFETCH_NARROW;
     const int p = lane % L::LPR, g = lane / L::LPR;
     RR buf[PF][L::C];
     u32 idb[PF];
@@ -554,12 +662,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
           }
           const Key key = key_make(dist, id);
           const bool pass = act && p == 0 && key_less(key, S.tau);
-          const u64 mm = __ballot(pass);
-          if (mm) {
-            if (pass) S.kbuf[S.kcnt + mask_rank(mm)] = key;
-            S.kcnt += __popcll(mm);
-            if (S.kcnt + L::RPW > S.cap) sel_shrink(S);
-          }
+          sel_offer(S, key, pass, L::RPW);
         }
       }
     }
@@ -604,12 +707,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
           }
           const Key key = key_make(dist, id);
           const bool pass = act && p == 0 && key_less(key, S.tau);
-          const u64 mm = __ballot(pass);
-          if (mm) {
-            if (pass) S.kbuf[S.kcnt + mask_rank(mm)] = key;
-            S.kcnt += __popcll(mm);
-            if (S.kcnt + rpw > S.cap) sel_shrink(S);
-          }
+          sel_offer(S, key, pass, rpw);
         }
       }
     }
@@ -942,7 +1040,10 @@ struct FusedTail {
   FT *top_dist;
 };
 
-template <int D, int SEG, bool FUSED, typename RT>  // SEG: 0 = slot scan, 1 = segment words + table rows, 2 = inline 32-byte records
+// SEG: 0 = slot scan, 1 = segment words + table rows, 2 = inline 32-byte records
+// REGS: the running selection lives in registers (SelRegs; the host chooses it where sel_regs_layout<D>() and
+// K1 <= ANN_SEL_REGS_KMAX): no kbuf, `cap` unused, kout for wave 0 only
+template <int D, int SEG, bool FUSED, typename RT, bool REGS>
 __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, const FT *__restrict__ y,
                                                             int alias, const u32 *__restrict__ codes,
                                                             int K1, int cap, u32 runs_used,
@@ -955,8 +1056,8 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
   // ---- LDS carve-up (mirrored by stage1_lds_bytes on the host)
   unsigned char *sp = smem;
-  Key *kbuf_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * cap;
-  Key *kout_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * K1;
+  Key *kbuf_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (REGS ? 0 : (size_t)W * cap);
+  Key *kout_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)(REGS ? 1 : W) * K1;
   Key *mbuf = reinterpret_cast<Key *>(sp);               sp += sizeof(Key) * (size_t)W * K1;
   TryInfo *tries = reinterpret_cast<TryInfo *>(sp);      sp += sizeof(TryInfo) * (size_t)P.T;
   const u32 **rptr_all = reinterpret_cast<const u32 **>(sp);  sp += sizeof(u32 *) * (size_t)W * ANN_WAVE;
@@ -989,9 +1090,10 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
     for (int z = threadIdx.x; z < P.d; z += blockDim.x) yq[z] = y[(size_t)x * P.d + z];
   __syncthreads();
 
-  SelState S;
-  S.kbuf = kbuf_all + (size_t)w * cap, S.kout = kout_all + (size_t)w * K1;
-  S.kcnt = 0, S.K1 = K1, S.cap = cap, S.tau = key_max();
+  static_assert(!REGS || sel_regs_layout<D>(), "this layout's gather has no register selection");
+  typename SelOf<REGS>::T S;
+  Key *const kout = kout_all + (REGS ? 0 : (size_t)w * K1);  // (REGS: written by wave 0 alone)
+  sel_init(S, kbuf_all + (REGS ? 0 : (size_t)w * cap), kout, K1, cap);
   FT *scratch = yq + (size_t)(1 + w) * P.d;
   u32 vtot = 0, vown = 0;
 
@@ -1144,8 +1246,7 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
 
   // ---- this wave's survivors -> merge buffer
   {
-    const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
-    for (int i = lane; i < m; i += ANN_WAVE) mbuf[(size_t)w * K1 + i] = S.kout[i];
+    const int m = sel_wave_result(S, mbuf + (size_t)w * K1);
     if (lane == 0) {
       mcnt[w] = m;
       atomicAdd(&cnts[0], vtot);
@@ -1154,21 +1255,14 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
   }
   __syncthreads();
   if (w == 0) {
-    int total = 0;
-    for (int ww = 0; ww < W; ww++) {  // cap >= W*K1 (host guarantees)
-      const int m = mcnt[ww];
-      for (int i = lane; i < m; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * K1 + i];
-      total += m;
-    }
-    wave_lds_sync();
-    const int m = wave_select_smallest(S.kbuf, total, K1, S.kout);
+    const int m = sel_merge(S, mbuf, mcnt, W, kout);
     if constexpr (!FUSED) {
       if (cand_key) {  // sharded hosts: one packed (dist,id) key per candidate, the unit their exchange moves
-        for (int i = lane; i < K1; i += ANN_WAVE) cand_key[(size_t)x * K1 + i] = i < m ? S.kout[i] : key_make(ft_inf(), ANN_ID_NONE);
+        for (int i = lane; i < K1; i += ANN_WAVE) cand_key[(size_t)x * K1 + i] = i < m ? kout[i] : key_make(ft_inf(), ANN_ID_NONE);
       } else {
         for (int i = lane; i < K1; i += ANN_WAVE) {
-          cand_dist[(size_t)x * K1 + i] = i < m ? key_dist(S.kout[i]) : ft_inf();
-          cand_id[(size_t)x * K1 + i] = i < m ? key_id(S.kout[i]) : ANN_ID_NONE;
+          cand_dist[(size_t)x * K1 + i] = i < m ? key_dist(kout[i]) : ft_inf();
+          cand_id[(size_t)x * K1 + i] = i < m ? key_id(kout[i]) : ANN_ID_NONE;
         }
       }
       if (lane == 0) {
@@ -1179,8 +1273,8 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
         const int k = K1 - 1;
         bool bad = m < k;
         for (int t = lane; t + 1 < m; t += ANN_WAVE)
-          if (ft_bits(key_dist(S.kout[t])) == ft_bits(key_dist(S.kout[t + 1]))) bad = true;
-        if (m >= k && !(key_dist(S.kout[k - 1]) < ft_inf())) bad = true;
+          if (ft_bits(key_dist(kout[t])) == ft_bits(key_dist(kout[t + 1]))) bad = true;
+        if (m >= k && !(key_dist(kout[k - 1]) < ft_inf())) bad = true;
         if (P.L1 > P.P1 && cnts[0] >= P.P1) bad = true;
         if (__ballot(bad) != 0) {
           if (lane == 0) {
@@ -1189,8 +1283,8 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
           }
         } else {
           for (int t = lane; t < k; t += ANN_WAVE) {
-            F.top_id[(size_t)x * k + t] = key_id(S.kout[t]);
-            F.top_dist[(size_t)x * k + t] = key_dist(S.kout[t]);
+            F.top_id[(size_t)x * k + t] = key_id(kout[t]);
+            F.top_dist[(size_t)x * k + t] = key_dist(kout[t]);
           }
         }
       }
@@ -1199,14 +1293,14 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
       const int k = K1 - 1;
       bool bad = m < k;
       for (int t = lane; t + 1 < m; t += ANN_WAVE)
-        if (ft_bits(key_dist(S.kout[t])) == ft_bits(key_dist(S.kout[t + 1]))) bad = true;
-      if (m >= k && !(key_dist(S.kout[k - 1]) < ft_inf())) bad = true;
+        if (ft_bits(key_dist(kout[t])) == ft_bits(key_dist(kout[t + 1]))) bad = true;
+      if (m >= k && !(key_dist(kout[k - 1]) < ft_inf())) bad = true;
       if (P.L1 > P.P1 && cnts[0] >= P.P1) bad = true;
       const bool reject = __ballot(bad) != 0;
       if (reject && cand_dist)  // the exact path's tie shortcut (ann_tie.h) wants the candidate list of a rejected query
         for (int i = lane; i < K1; i += ANN_WAVE) {
-          cand_dist[(size_t)x * K1 + i] = i < m ? key_dist(S.kout[i]) : ft_inf();
-          cand_id[(size_t)x * K1 + i] = i < m ? key_id(S.kout[i]) : ANN_ID_NONE;
+          cand_dist[(size_t)x * K1 + i] = i < m ? key_dist(kout[i]) : ft_inf();
+          cand_id[(size_t)x * K1 + i] = i < m ? key_id(kout[i]) : ANN_ID_NONE;
         }
       if (lane == 0) {
         cnts[3] = reject ? 1u : 0u;
@@ -1231,6 +1325,45 @@ __global__ __launch_bounds__(256) void stage1_select_kernel(QParams P, int Q, co
   }
   }  // FUSED
   }  // queries of this workgroup
+}
+
+// Test hook (annhip_test_select): stage 1's selection on caller-supplied key streams, through the device functions
+// stage1_select_kernel calls.  One workgroup per stream [off[b], off[b + 1]); wave w takes the 64-key passes w, w + W, ...
+// and offers them as gather_select does (key < tau vector-side, then sel_offer); then sel_wave_result, the barrier and
+// wave 0's sel_merge.  Output per stream: K1 ascending distinct keys padded with (+inf, ANN_ID_NONE).
+template <bool REGS>
+__global__ __launch_bounds__(256) void test_select_kernel(const u32 *__restrict__ off, const FT *__restrict__ dist,
+                                                          const u32 *__restrict__ id, int K1, int cap,
+                                                          FT *__restrict__ out_dist, u32 *__restrict__ out_id) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
+  // ---- LDS carve-up (mirrored by annhip_test_select on the host)
+  unsigned char *sp = smem;
+  Key *kbuf_all = reinterpret_cast<Key *>(sp);  sp += sizeof(Key) * (REGS ? 0 : (size_t)W * cap);
+  Key *kout_all = reinterpret_cast<Key *>(sp);  sp += sizeof(Key) * (size_t)(REGS ? 1 : W) * K1;
+  Key *mbuf = reinterpret_cast<Key *>(sp);      sp += sizeof(Key) * (size_t)W * K1;
+  int *mcnt = reinterpret_cast<int *>(sp);
+  typename SelOf<REGS>::T S;
+  Key *const kout = kout_all + (REGS ? 0 : (size_t)w * K1);
+  sel_init(S, kbuf_all + (REGS ? 0 : (size_t)w * cap), kout, K1, cap);
+  const u32 b = blockIdx.x, s0 = off[b], s1 = off[b + 1];
+  for (u32 base = s0 + (u32)w * ANN_WAVE; base < s1; base += (u32)W * ANN_WAVE) {
+    const u32 i = base + lane;
+    const bool in = i < s1;
+    const Key key = in ? key_make(dist[i], id[i]) : key_max();
+    sel_offer(S, key, in && key_less(key, S.tau), ANN_WAVE);
+  }
+  wave_lds_sync();
+  const int mw = sel_wave_result(S, mbuf + (size_t)w * K1);
+  if (lane == 0) mcnt[w] = mw;
+  __syncthreads();
+  if (w == 0) {
+    const int m = sel_merge(S, mbuf, mcnt, W, kout);
+    for (int i = lane; i < K1; i += ANN_WAVE) {
+      out_dist[(size_t)b * K1 + i] = i < m ? key_dist(kout[i]) : ft_inf();
+      out_id[(size_t)b * K1 + i] = i < m ? key_id(kout[i]) : ANN_ID_NONE;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------- stage1_bucket

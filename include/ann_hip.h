@@ -483,6 +483,14 @@ void annhip_test_sort_rows(size_t L, size_t k, size_t nq, uint32_t *ids_dev, fty
                            const uint32_t *cand_i_dev, uint32_t *out_id_dev, ftype *out_dist_dev,
                            unsigned long long *resolved_dev, int derive);
 
+/* Test hook: stage 1's running selection of the K1 smallest distinct (distance, id) keys, run by the device functions the
+ * stage-1 kernel itself calls, on ns free-standing key streams: stream b is dist_dev / id_dev [off_dev[b], off_dev[b+1])
+ * (off_dev: ns + 1 ascending offsets), split over W waves (1..4) whose results wave 0 merges.  lds == 0: the register
+ * list (K1 <= 128); lds != 0: the LDS candidate buffer (K1 <= 256).  out_*_dev [ns][K1]: the keys ascending, padded with
+ * (+inf, 0xFFFFFFFF).  Synchronous.  Returns 0, or -1 for arguments outside those ranges. */
+int annhip_test_select(size_t ns, const uint32_t *off_dev, const ftype *dist_dev, const uint32_t *id_dev, size_t K1, int W,
+                       int lds, ftype *out_dist_dev, uint32_t *out_id_dev);
+
 /* ---- content checksums (device memory in, 64-bit value out; synchronous) ------------------------------------------- */
 /* annhip_checksum_dev: checksum of nbytes of device memory (4-byte aligned), independent of the launch geometry.
  * annhip_index_checksum: geometry, every bucket table, graph, means and projection rows of a resident index -- everything

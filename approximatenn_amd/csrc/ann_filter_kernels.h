@@ -4,16 +4,16 @@
 // The allow list is a bitmap, u32 bits[ceil(n / 32)]: row i is allowed iff bits[i >> 5] >> (i & 31) & 1.  A filter only
 // narrows what fixed mode calls a valid id, so the kernels here are the fixed-mode kernels with one more test:
 //
-//   stage1_filter    stage1_probe_kernel's structure (runs decoded as (try, mask), pb = 0 gives the plain 1 + ds buckets
-//                    of fixed mode).  The bit test sits where an id ENTERS the wave's LDS list: a disallowed row is never
-//                    fetched, the gather (probe_gather, unchanged) still runs one dependent step after the list.
-//   stage2_filter    stage2_select_kernel with the bit test in its `ok` predicate
+//   AdmitBits        the bit test as an admission policy: it sits where an id ENTERS the wave's LDS list, so a
+//                    disallowed row is never fetched
+//   stage1_filter    stage1_fixed_body's tested form (ann_probe_kernels.h) with the bit test, as a copy of its own
+//   stage2_fixed_body   stage2_select_kernel with the policy in its `ok` predicate: stage 2 of the filter and tag
+//                    families; stage2_filter is its entry point for the allow list
 //   filter_pack      u8 flags -> bitmap;   filter_count   popcount of bits [0, n)
 //   exact_scan_filtered / exact_scan_generic_filtered   the exact scan's two kernels with the tile's bitmap words in LDS
 //   exact_tail       the exact scan's "no row" padding -> (n, +inf)
 //
-// The bitmap is a separate kernel argument everywhere: QParams and the existing kernels are not touched, and an
-// unfiltered query launches exactly the kernels it launched before.
+// The bitmap is a separate kernel argument everywhere, and an unfiltered query launches nothing from this file.
 #pragma once
 #include "ann_exact_kernels.h"
 #include "ann_probe_kernels.h"
@@ -21,9 +21,17 @@
 // id < n (the caller's test): the word is inside the bitmap
 __device__ __forceinline__ bool filter_allows(const u32 *__restrict__ bits, u32 id) { return (bits[id >> 5] >> (id & 31u)) & 1u; }
 
+// the admission policy of the allow list (see stage1_fixed_body)
+struct AdmitBits {
+  static constexpr bool ALWAYS = false;
+  const u32 *__restrict__ bits;
+  __device__ __forceinline__ bool operator()(u32 id) const { return filter_allows(bits, id); }
+};
+
 // ------------------------------------------------------------------------------------------ stage 1
-// As stage1_probe_kernel, except for phase A: the ids of the probed buckets pass the bit test on their way into the list,
-// 64 at a time, ballot-compacted (SEG: walking the concatenation of the runs' segments; !SEG: walking the slots).
+// stage1_fixed_body's tested form (ann_probe_kernels.h) with the bit test, kept as its own copy: shared through the body,
+// three instances of this kernel need more registers than they have here and lose a wave per SIMD
+// (profiles/fixed_body_devcode.md).  A fix to the body's segment walk, list or merge has to be made here as well.
 // nv_tot = valid ids seen, as before; nv_own = ids in the list = rows gathered = allowed valid ids (self included when
 // allowed: the gather drops it).
 template <int D, bool SEG, typename RT>
@@ -35,7 +43,7 @@ __global__ __launch_bounds__(256) void stage1_filter_kernel(QParams P, const FT 
                                                             u32 *__restrict__ nv_tot, u32 *__restrict__ nv_own) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  // ---- LDS carve-up: stage1_probe_kernel's (stage1_probe_lds_bytes on the host)
+  // ---- LDS carve-up: stage1_fixed_body's (stage1_probe_lds_bytes on the host)
   unsigned char *sp = smem;
   Key *kbuf_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * cap;
   Key *kout_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * K1;
@@ -197,17 +205,14 @@ __global__ __launch_bounds__(256) void stage1_filter_kernel(QParams P, const FT 
 
 // ------------------------------------------------------------------------------------------ stage 2
 // stage2_select_kernel (same arguments, same LDS carve-up, same rejection rule outside fixed mode) over the stage-1
-// results and the ALLOWED graph neighbours of those results: `ok` gains the bit test.  The stage-1 results enter with the
-// distances they have; stage1_filter_kernel returns allowed rows only.  The gather goes through probe_gather: the same
-// arithmetic as gather_select, without the 72-byte private segment the folded layouts' FoldPlan constructor costs.
-template <int D, typename IdOut, typename RT>
-__global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, const FT *__restrict__ y, int alias,
-                                                            const u32 *__restrict__ top_id, const FT *__restrict__ top_dist,
-                                                            const u32 *__restrict__ bits, u32 P2, int K1, int cap,
-                                                            IdOut *__restrict__ out_ids, FT *__restrict__ out_dist,
-                                                            u32 *__restrict__ flist, u32 *__restrict__ fcount,
-                                                            unsigned long long *__restrict__ exact_total,
-                                                            unsigned long long *__restrict__ rows_done, u32 xbase) {
+// results and the ADMITTED graph neighbours of those results: `ok` gains adm().  The stage-1 results enter with the
+// distances they have; stage 1 of the same family returns admitted rows only.  The gather goes through probe_gather: the
+// same arithmetic as gather_select, without the 72-byte private segment the folded layouts' FoldPlan constructor costs.
+template <int D, typename IdOut, typename RT, typename Admit>
+__device__ __forceinline__ void stage2_fixed_body(const QParams &P, const FT *y, int alias, const u32 *top_id,
+                                                  const FT *top_dist, const Admit &adm, u32 P2, int K1, int cap,
+                                                  IdOut *out_ids, FT *out_dist, u32 *flist, u32 *fcount,
+                                                  unsigned long long *exact_total, unsigned long long *rows_done, u32 xbase) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
   const u32 x = xbase + blockIdx.x;
@@ -229,16 +234,7 @@ __global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, co
   if constexpr (D == 0 || OcCode<D>::GEN)
     for (int z = threadIdx.x; z < P.d; z += blockDim.x) yq[z] = y[(size_t)x * P.d + z];
   VT a[RowChunks<D>::C];
-  if constexpr (D > 0) {
-    typedef RowLay<D> L;
-    const VT *yp = reinterpret_cast<const VT *>(y + (size_t)x * D) + (lane % L::LPR);
-#pragma unroll
-    for (int c = 0; c < L::C; c++) a[c] = yp[c * L::LPR];
-  } else if constexpr (D < 0 && !OcCode<D>::GEN) {
-    const OcLanes<D> ol(P.d, lane);
-#pragma unroll
-    for (int c = 0; c < OcCode<D>::C; c++) a[c] = oc_load_chunk<D, false>(y + (size_t)x * P.d, ol.p + c * ol.oc, P.d);
-  }
+  load_query_slice<D>(P, y, x, lane, a);
   __syncthreads();
 
   SelState S;
@@ -261,7 +257,7 @@ __global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, co
       } else {
         const u32 parent = key_id(top[j / k - 1]), z = j % k;
         id = parent < P.n ? P.graph[(size_t)parent * k + z] : (P.graph[z] | P.n);  // supercharge, Q7
-        ok = id < P.n && !(alias && id == x) && id >= P.lo && id < P.hi && filter_allows(bits, id);
+        ok = id < P.n && !(alias && id == x) && id >= P.lo && id < P.hi && adm(id);
       }
     }
     nfin += __popcll(__ballot(direct || ok));
@@ -272,39 +268,15 @@ __global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, co
       if (push) S.kbuf[S.kcnt + mask_rank(dm)] = dk;
       S.kcnt += __popcll(dm);
     }
-    const u64 mm = __ballot(ok);
-    if (ok) list[cnt + mask_rank(mm)] = id;
-    cnt += __popcll(mm);
-    if (cnt + ANN_WAVE > ANN_S1_CHUNK) {
-      wave_lds_sync();
-      vown += cnt;
-      probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
-      cnt = 0;
-    }
+    list_push<D, RT>(ok, id, P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
   }
-  wave_lds_sync();
-  vown += cnt;
-  probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  list_flush<D, RT>(P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
 
-  {  // this wave's survivors -> merge buffer
-    const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
-    for (int i = lane; i < m; i += ANN_WAVE) mbuf[(size_t)w * K1 + i] = S.kout[i];
-    if (lane == 0) {
-      mcnt[w] = m;
-      atomicAdd(&cnts[0], nfin);
-      atomicAdd(&cnts[1], vown);
-    }
-  }
-  __syncthreads();
+  const int m = merge_waves(S, mbuf, mcnt, w, W, K1, [&] {
+    atomicAdd(&cnts[0], nfin);
+    atomicAdd(&cnts[1], vown);
+  });
   if (w == 0) {
-    int total = 0;
-    for (int ww = 0; ww < W; ww++) {  // cap >= W*K1 (host guarantees)
-      const int m = mcnt[ww];
-      for (int i = lane; i < m; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * K1 + i];
-      total += m;
-    }
-    wave_lds_sync();
-    const int m = wave_select_smallest(S.kbuf, total, K1, S.kout);
     bool bad = m < k;
     for (int t = lane; t + 1 < m; t += ANN_WAVE)
       if (ft_bits(key_dist(S.kout[t])) == ft_bits(key_dist(S.kout[t + 1]))) bad = true;
@@ -324,6 +296,18 @@ __global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, co
     }
     if (rows_done && lane == 0) atomicAdd(&rows_done[(x & 63u) * 8u], (unsigned long long)cnts[1]);
   }
+}
+
+template <int D, typename IdOut, typename RT>
+__global__ __launch_bounds__(256) void stage2_filter_kernel(QParams P, int Q, const FT *__restrict__ y, int alias,
+                                                            const u32 *__restrict__ top_id, const FT *__restrict__ top_dist,
+                                                            const u32 *__restrict__ bits, u32 P2, int K1, int cap,
+                                                            IdOut *__restrict__ out_ids, FT *__restrict__ out_dist,
+                                                            u32 *__restrict__ flist, u32 *__restrict__ fcount,
+                                                            unsigned long long *__restrict__ exact_total,
+                                                            unsigned long long *__restrict__ rows_done, u32 xbase) {
+  stage2_fixed_body<D, IdOut, RT>(P, y, alias, top_id, top_dist, AdmitBits{bits}, P2, K1, cap, out_ids, out_dist, flist, fcount,
+                                  exact_total, rows_done, xbase);
 }
 
 // ------------------------------------------------------------------------------------------ bitmap helpers

@@ -1295,66 +1295,21 @@ static size_t stage1_probe_lds_bytes(const QParams &P, int W, int K1, int cap, i
   return b;
 }
 
-// Stage 1 of fixed mode over 1 + ds + pb (pb - 1) / 2 buckets per try.  Waves per query from the RUN count: a run holds
-// at most par_maxes[t] ids, and a wave should see about a list (ANN_S1_CHUNK) of them to amortise its selection and the
-// merge -- the rule stage1_waves applies to P1, which says nothing about the pair runs.
-static void launch_stage1_probe(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
-                                const unsigned char *pbits, int pb, FT *cand_d, u32 *cand_i, u32 *nvt, u32 *nvo, hipStream_t s) {
-  if (!Q) return;
-  const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
-  size_t slots = 0;
-  for (int t = 0; t < P.T; t++) slots += (size_t)rpt * ix->h_tries[t].pm;
-  int W = (int)std::min<size_t>(4, std::max<size_t>(1, slots / ANN_S1_CHUNK));
-  if (env().s1_waves) W = env().s1_waves;
-  const int K1 = P.k + 1, cap = stage1_cap(W, K1);
-  const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
-  EventPair ev;
-  const bool prof = ix->profile;
-  if (prof) {
-    if (ix->ev_free.empty()) {
-      HIPCHECK(hipEventCreate(&ev.a));
-      HIPCHECK(hipEventCreate(&ev.b));
-    } else {
-      ev = ix->ev_free.back();
-      ix->ev_free.pop_back();
-    }
-    HIPCHECK(hipEventRecord(ev.a, s));
-  }
-  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
-    with_rows(P, [&](auto rt) {
-      auto launch = [&](auto sg) {
-        constexpr int D = decltype(dd)::value;
-        constexpr bool SG = decltype(sg)::value;
-        using RT = typename decltype(rt)::type;
-        allow_lds(stage1_probe_kernel<D, SG, RT>, smem);
-        hipLaunchKernelGGL((stage1_probe_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
-                           pb, rpt, K1, cap, cand_d, cand_i, nvt, nvo);
-      };
-      if (ix->use_seg) launch(std::true_type{});
-      else launch(std::false_type{});
-    });
-  });
-  HIPCHECK(hipGetLastError());
-  if (prof) {
-    HIPCHECK(hipEventRecord(ev.b, s));
-    ix->ev_used.push_back(ev);
-    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
-  }
-  ix->s1_launches += 1;
-}
-
 // The per-query tag predicate of one annhip_query_tagged call (ann_tag_kernels.h): the rows' tag words and the batch's
 // (mask, value) arrays, all on the device.
 struct TagQuery {
   const u32 *tags, *qmask, *qvalue;
 };
 
-// Stage 1 of fixed mode with an allow list (annhip_index_set_filter; ann_filter_kernels.h): launch_stage1_probe's shape
-// for every pair-bit setting, pb = 0 included (1 + ds runs per try, no ranked bits).  tq: annhip_query_tagged's stage 1,
-// the same shape with stage1_tag_kernel (bits may then be NULL).
-static void launch_stage1_filter(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
-                                 const unsigned char *pbits, int pb, const u32 *bits, FT *cand_d, u32 *cand_i, u32 *nvt,
-                                 u32 *nvo, hipStream_t s, const TagQuery *tq = NULL) {
+// Stage 1 of fixed mode over 1 + ds + pb (pb - 1) / 2 buckets per try (pb = 0: the plain 1 + ds, no ranked bits), for
+// every family that walks the (try, mask) runs (stage1_fixed_body in ann_probe_kernels.h and its two copies): with a radius
+// stage1_radius_kernel (bits and tq may each be NULL), else with tq stage1_tag_kernel (bits may be NULL), else with bits
+// stage1_filter_kernel, else stage1_probe_kernel.  Waves per query from the RUN count: a run holds at most par_maxes[t]
+// ids, and a wave should see about a list (ANN_S1_CHUNK) of them to amortise its selection and the merge -- the rule
+// stage1_waves applies to P1, which says nothing about the pair runs.
+static void launch_stage1_fixed(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
+                                const unsigned char *pbits, int pb, const u32 *bits, const TagQuery *tq, const FT *radius,
+                                FT *cand_d, u32 *cand_i, u32 *nvt, u32 *nvo, hipStream_t s) {
   if (!Q) return;
   const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
   size_t slots = 0;
@@ -1363,44 +1318,40 @@ static void launch_stage1_filter(annhip_index *ix, const QParams &P, size_t Q, c
   if (env().s1_waves) W = env().s1_waves;
   const int K1 = P.k + 1, cap = stage1_cap(W, K1);
   const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
+  const u32 *tags = tq ? tq->tags : NULL, *qmask = tq ? tq->qmask : NULL, *qvalue = tq ? tq->qvalue : NULL;
   EventPair ev;
-  const bool prof = ix->profile;
-  if (prof) {
-    if (ix->ev_free.empty()) {
-      HIPCHECK(hipEventCreate(&ev.a));
-      HIPCHECK(hipEventCreate(&ev.b));
-    } else {
-      ev = ix->ev_free.back();
-      ix->ev_free.pop_back();
-    }
-    HIPCHECK(hipEventRecord(ev.a, s));
-  }
+  if (ix->profile) ev = s1_prof_begin(ix, s);
   with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
     with_rows(P, [&](auto rt) {
       auto launch = [&](auto sg) {
         constexpr int D = decltype(dd)::value;
         constexpr bool SG = decltype(sg)::value;
         using RT = typename decltype(rt)::type;
-        if (tq) {
+        const dim3 grid((unsigned)Q), block(64 * W);
+        if (radius) {
+          allow_lds(stage1_radius_kernel<D, SG, RT>, smem);
+          hipLaunchKernelGGL((stage1_radius_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, radius,
+                             tags, bits, qmask, qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
+        } else if (tq) {
           allow_lds(stage1_tag_kernel<D, SG, RT>, smem);
-          hipLaunchKernelGGL((stage1_tag_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
-                             pb, rpt, tq->tags, bits, tq->qmask, tq->qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
-          return;
+          hipLaunchKernelGGL((stage1_tag_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, tags, bits,
+                             qmask, qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
+        } else if (bits) {
+          allow_lds(stage1_filter_kernel<D, SG, RT>, smem);
+          hipLaunchKernelGGL((stage1_filter_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, bits, K1,
+                             cap, cand_d, cand_i, nvt, nvo);
+        } else {
+          allow_lds(stage1_probe_kernel<D, SG, RT>, smem);
+          hipLaunchKernelGGL((stage1_probe_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, K1, cap,
+                             cand_d, cand_i, nvt, nvo);
         }
-        allow_lds(stage1_filter_kernel<D, SG, RT>, smem);
-        hipLaunchKernelGGL((stage1_filter_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
-                           pb, rpt, bits, K1, cap, cand_d, cand_i, nvt, nvo);
       };
       if (ix->use_seg) launch(std::true_type{});
       else launch(std::false_type{});
     });
   });
   HIPCHECK(hipGetLastError());
-  if (prof) {
-    HIPCHECK(hipEventRecord(ev.b, s));
-    ix->ev_used.push_back(ev);
-    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
-  }
+  if (ix->profile) s1_prof_end(ix, ev, Q, nvo, s);
   ix->s1_launches += 1;
 }
 
@@ -1766,9 +1717,8 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
     nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
     u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-    if (ix->filter || tq)  // allow list, tag predicate: one kernel family each for every pair-bit setting (b = 0: no ranked bits)
-      launch_stage1_filter(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s, tq);
-    else if (probing) launch_stage1_probe(ix, P, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
+    if (ix->filter || tq || probing)  // one kernel family each, for every pair-bit setting (b = 0: no ranked bits)
+      launch_stage1_fixed(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, NULL, cand_d, cand_i, nvt, nvo, s);
     else launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
     seg_mark(ix, marks, s);
     hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, P.k, K1, P.L1, P.P1,
@@ -2057,9 +2007,8 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
   u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
   u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-  if (ix->filter || tq)
-    launch_stage1_filter(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, cand_d, cand_i, nvt, nvo, s, tq);
-  else if (probing) launch_stage1_probe(ix, P1, Q, y, alias, codes, pbits, ix->probe, cand_d, cand_i, nvt, nvo, s);
+  if (ix->filter || tq || probing)
+    launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, NULL, cand_d, cand_i, nvt, nvo, s);
   else launch_stage1(ix, P1, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
   seg_mark(ix, marks, s);
   hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kq, K1, P.L1, P.P1, cand_d,
@@ -2104,55 +2053,6 @@ extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip
 
 // ----------------------------------------------------------------------------- radius queries (annhip_query_radius)
 // Contract: include/ann_hip.h.  Kernels: ann_radius_kernels.h.
-// Stage 1 of a radius query: launch_stage1_filter's shape (wave rule, profiling events, s1_launches) with
-// stage1_radius_kernel, for every pair-bit setting, with or without an allow list (bits) and tags (tq).
-static void launch_stage1_radius(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int alias, const u32 *codes,
-                                 const unsigned char *pbits, int pb, const FT *radius, const u32 *bits, FT *cand_d, u32 *cand_i,
-                                 u32 *nvt, u32 *nvo, hipStream_t s, const TagQuery *tq) {
-  if (!Q) return;
-  const u32 rpt = 1u + (u32)P.ds + (u32)(pb * (pb - 1) / 2);
-  size_t slots = 0;
-  for (int t = 0; t < P.T; t++) slots += (size_t)rpt * ix->h_tries[t].pm;
-  int W = (int)std::min<size_t>(4, std::max<size_t>(1, slots / ANN_S1_CHUNK));
-  if (env().s1_waves) W = env().s1_waves;
-  const int K1 = P.k + 1, cap = stage1_cap(W, K1);
-  const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
-  EventPair ev;
-  const bool prof = ix->profile;
-  if (prof) {
-    if (ix->ev_free.empty()) {
-      HIPCHECK(hipEventCreate(&ev.a));
-      HIPCHECK(hipEventCreate(&ev.b));
-    } else {
-      ev = ix->ev_free.back();
-      ix->ev_free.pop_back();
-    }
-    HIPCHECK(hipEventRecord(ev.a, s));
-  }
-  with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
-    with_rows(P, [&](auto rt) {
-      auto launch = [&](auto sg) {
-        constexpr int D = decltype(dd)::value;
-        constexpr bool SG = decltype(sg)::value;
-        using RT = typename decltype(rt)::type;
-        allow_lds(stage1_radius_kernel<D, SG, RT>, smem);
-        hipLaunchKernelGGL((stage1_radius_kernel<D, SG, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, codes, pbits,
-                           pb, rpt, radius, tq ? tq->tags : (const u32 *)NULL, bits, tq ? tq->qmask : (const u32 *)NULL,
-                           tq ? tq->qvalue : (const u32 *)NULL, K1, cap, cand_d, cand_i, nvt, nvo);
-      };
-      if (ix->use_seg) launch(std::true_type{});
-      else launch(std::false_type{});
-    });
-  });
-  HIPCHECK(hipGetLastError());
-  if (prof) {
-    HIPCHECK(hipEventRecord(ev.b, s));
-    ix->ev_used.push_back(ev);
-    if (ix->profile == 1) sum_u32_kernel<<<grid_for(Q, 256, 64), 256, 0, s>>>(Q, nvo, ix->d_rows);
-  }
-  ix->s1_launches += 1;
-}
-
 static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *radius, size_t *ids, FT *dists, u32 *counts,
                                hipStream_t s) {
   if (!Q || !kcap) return;
@@ -2192,8 +2092,7 @@ static long query_radius_impl(annhip_index *ix, annhip_workspace &ws, hipStream_
   u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
   u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
   u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-  launch_stage1_radius(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, radius, ix->filter, cand_d, cand_i, nvt, nvo, s,
-                       tq);
+  launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, radius, cand_d, cand_i, nvt, nvo, s);
   seg_mark(ix, marks, s);
   hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kcap, K1, P.L1, P.P1,
                      cand_d, cand_i, nvt, top_i, top_d, (int)kcap, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);

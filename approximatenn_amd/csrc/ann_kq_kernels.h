@@ -19,9 +19,10 @@
 // is its FLOORED quotient and remainder, so the lanes that start among the stage-1 results (g < 0, p < 0) walk into the
 // graph part by the same rule; exact for every kg >= 1 and every slot index below 2^31 (the host refuses longer rows).
 //
-// The gather goes through probe_gather (ann_probe_kernels.h) like the filter and tag families: the arithmetic of
-// gather_select without the private segment that FoldPlan's constructor costs the folded layouts.  QParams and the
-// existing kernels are not touched; no call but annhip_query_k launches anything from this file.
+// The slot walk and the kq-wide output are this kernel's own; the query-row load, the list and the merge are the pieces
+// it shares with the fixed-mode bodies (ann_probe_kernels.h), probe_gather included: the arithmetic of gather_select
+// without the private segment that FoldPlan's constructor costs the folded layouts.  No call but annhip_query_k and the
+// radius entry points launches anything from this file.
 #pragma once
 #include "ann_tag_kernels.h"
 
@@ -58,16 +59,7 @@ __global__ __launch_bounds__(256) void stage2_kq_kernel(QParams P, const FT *__r
   if constexpr (D == 0 || OcCode<D>::GEN)
     for (int z = threadIdx.x; z < P.d; z += blockDim.x) yq[z] = y[(size_t)x * P.d + z];
   VT a[RowChunks<D>::C];
-  if constexpr (D > 0) {
-    typedef RowLay<D> L;
-    const VT *yp = reinterpret_cast<const VT *>(y + (size_t)x * D) + (lane % L::LPR);
-#pragma unroll
-    for (int c = 0; c < L::C; c++) a[c] = yp[c * L::LPR];
-  } else if constexpr (D < 0 && !OcCode<D>::GEN) {
-    const OcLanes<D> ol(P.d, lane);
-#pragma unroll
-    for (int c = 0; c < OcCode<D>::C; c++) a[c] = oc_load_chunk<D, false>(y + (size_t)x * P.d, ol.p + c * ol.oc, P.d);
-  }
+  load_query_slice<D>(P, y, x, lane, a);
   __syncthreads();
 
   SelState S;
@@ -113,40 +105,14 @@ __global__ __launch_bounds__(256) void stage2_kq_kernel(QParams P, const FT *__r
       if (push) S.kbuf[S.kcnt + mask_rank(dm)] = dk;
       S.kcnt += __popcll(dm);
     }
-    const u64 mm = __ballot(ok);
-    if (ok) list[cnt + mask_rank(mm)] = id;
-    cnt += __popcll(mm);
-    if (cnt + ANN_WAVE > ANN_S1_CHUNK) {
-      wave_lds_sync();
-      vown += cnt;
-      probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
-      cnt = 0;
-    }
+    list_push<D, RT>(ok, id, P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
     z += r64, p += q64;  // 64 slots further
     if (z >= kg) z -= kg, p++;
   }
-  wave_lds_sync();
-  vown += cnt;
-  probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  list_flush<D, RT>(P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
 
-  {  // this wave's survivors -> merge buffer
-    const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
-    for (int i = lane; i < m; i += ANN_WAVE) mbuf[(size_t)w * K1 + i] = S.kout[i];
-    if (lane == 0) {
-      mcnt[w] = m;
-      atomicAdd(&cnts[1], vown);
-    }
-  }
-  __syncthreads();
+  const int m = merge_waves(S, mbuf, mcnt, w, W, K1, [&] { atomicAdd(&cnts[1], vown); });
   if (w == 0) {
-    int total = 0;
-    for (int ww = 0; ww < W; ww++) {  // cap >= W*K1 (host guarantees)
-      const int m = mcnt[ww];
-      for (int i = lane; i < m; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * K1 + i];
-      total += m;
-    }
-    wave_lds_sync();
-    const int m = wave_select_smallest(S.kbuf, total, K1, S.kout);
     for (int t = lane; t < kq; t += ANN_WAVE) {  // the kq smallest distinct keys in (distance, id) order, (n, +inf) where fewer exist
       out_ids[(size_t)x * kq + t] = t < m ? (IdOut)key_id(S.kout[t]) : (IdOut)P.n;
       out_dist[(size_t)x * kq + t] = t < m ? key_dist(S.kout[t]) : ft_inf();

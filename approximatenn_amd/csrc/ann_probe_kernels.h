@@ -3,15 +3,19 @@
 // Fixed mode looks, per try, into the query's own bucket and the ds buckets at Hamming distance 1.  With "pair bits"
 // b > 0 it also looks into the C(b,2) buckets reached by flipping TWO of the query's b least certain hash bits: the
 // hash is the sign of ds projections, and a projection close to zero is a bit that is likely to differ for a true
-// neighbour.  Two kernels:
+// neighbour.
 //
 //   codes_probe_lpq / codes_probe   the hash kernels' dot products, literally (same tree, same "+ 0": the codes are
 //                                   bit-identical to codes_lpq_kernel / codes_kernel), plus the ranking: per (query, try)
 //                                   the b projection indices of smallest magnitude, ascending by (|p| bits, s)
-//   stage1_probe                    stage1_select_kernel's structure with the run index decoded as (try, mask):
-//                                   masks 0, 1<<z, and bit(o[u]) | bit(o[v]) for u < v < b
+//   stage1_fixed_body               stage 1 of the fixed-mode families that decode their runs as (try, mask) -- masks 0,
+//                                   1<<z, and bit(o[u]) | bit(o[v]) for u < v < b -- with admission to the wave's list as
+//                                   a policy type; stage1_probe is its entry point that admits every valid id, stage1_tag
+//                                   (ann_tag_kernels.h) the one with a test.  stage1_filter and stage1_radius keep a copy
+//                                   of its tested form in their own headers (the reason is given there).
+//   load_query_slice, list_push / list_flush, merge_waves   the pieces that body shares with the stage-2 bodies
 //
-// The existing kernels are not touched; b = 0 launches them as before.
+// b = 0 without a filter, tags or a radius launches stage1_select_kernel as before.
 #pragma once
 #include "ann_query_kernels.h"
 
@@ -263,23 +267,107 @@ __device__ __forceinline__ void probe_gather(const QParams &P, const u32 *list, 
   }
 }
 
+// ------------------------------------------------------------------------------------------ shared pieces
+// What the fixed-mode bodies (stage1_fixed_body here, stage2_fixed_body in ann_filter_kernels.h, stage2_kq_kernel) have
+// in common.  Everything is forced inline: an entry point compiles to the code it had when it spelled these out.
+
+// The query row, as this lane's slice (the generic layouts read it from LDS instead: yq).
+template <int D>
+__device__ __forceinline__ void load_query_slice(const QParams &P, const FT *y, u32 x, int lane, VT (&a)[RowChunks<D>::C]) {
+  if constexpr (D > 0) {
+    typedef RowLay<D> L;
+    const VT *yp = reinterpret_cast<const VT *>(y + (size_t)x * D) + (lane % L::LPR);
+#pragma unroll
+    for (int c = 0; c < L::C; c++) a[c] = yp[c * L::LPR];
+  } else if constexpr (D < 0 && !OcCode<D>::GEN) {
+    const OcLanes<D> ol(P.d, lane);
+#pragma unroll
+    for (int c = 0; c < OcCode<D>::C; c++) a[c] = oc_load_chunk<D, false>(y + (size_t)x * P.d, ol.p + c * ol.oc, P.d);
+  }
+}
+
+// The wave's id list: ANN_S1_CHUNK ids in LDS, cnt of them in use; vown counts the rows gathered.  list_flush gathers the
+// listed rows into the selection and empties the list; list_push appends the ids of the lanes whose `own` is set
+// (ballot-compacted) and flushes when another 64 might not fit.
+template <int D, typename RT>
+__device__ __forceinline__ void list_flush(const QParams &P, const u32 *list, int &cnt, u32 &vown, int alias, u32 x,
+                                           const VT (&a)[RowChunks<D>::C], const FT *yq, FT *scratch, SelState &S,
+                                           const FT *y) {
+  wave_lds_sync();
+  vown += cnt;
+  probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  cnt = 0;
+}
+template <int D, typename RT>
+__device__ __forceinline__ void list_push(bool own, u32 id, const QParams &P, u32 *list, int &cnt, u32 &vown, int alias,
+                                          u32 x, const VT (&a)[RowChunks<D>::C], const FT *yq, FT *scratch, SelState &S,
+                                          const FT *y) {
+  const u64 mm = __ballot(own);
+  if (own) list[cnt + mask_rank(mm)] = id;
+  cnt += __popcll(mm);
+  if (cnt + ANN_WAVE > ANN_S1_CHUNK) list_flush<D, RT>(P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
+}
+
+// The end of a body: this wave's survivors -> mbuf / mcnt (lane 0 then runs `tally`, the workgroup's counters), barrier,
+// wave 0 gathers the waves' survivors and selects.  Returns m, the number of distinct keys in S.kout, ascending (wave 0;
+// 0 in the other waves).  cap >= W * K1 (the host guarantees).
+template <typename Tally>
+__device__ __forceinline__ int merge_waves(SelState &S, Key *mbuf, int *mcnt, int w, int W, int K1, Tally tally) {
+  const int lane = lane_id();
+  {
+    const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
+    for (int i = lane; i < m; i += ANN_WAVE) mbuf[(size_t)w * K1 + i] = S.kout[i];
+    if (lane == 0) {
+      mcnt[w] = m;
+      tally();
+    }
+  }
+  __syncthreads();
+  int m = 0;
+  if (w == 0) {
+    int total = 0;
+    for (int ww = 0; ww < W; ww++) {
+      const int mw = mcnt[ww];
+      for (int i = lane; i < mw; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * K1 + i];
+      total += mw;
+    }
+    wave_lds_sync();
+    m = wave_select_smallest(S.kbuf, total, K1, S.kout);
+  }
+  return m;
+}
+
+// ------------------------------------------------------------------------------------------ stage 1, every family
+// Admission: which valid ids of a probed bucket enter the wave's list.  A policy is built once per workgroup from the
+// kernel's own arguments and x, offers operator()(id) for id < n, and says with ALWAYS whether the test is vacuous.
+struct AdmitAll {
+  static constexpr bool ALWAYS = true;
+  __device__ __forceinline__ bool operator()(u32) const { return true; }
+};
+
 // One workgroup per query (blockIdx.x); its waves split the T * rpt (try, mask) runs.  Per wave, as stage1_select_kernel:
-//   A) SEG: segment word of each run's bucket -> the owned ids into the wave's LDS list (prefix sum, balanced copy);
-//      !SEG (a table without the sorted-prefix layout): every slot of the run's bucket row, ballot-compacted;
-//   B) gather_select whenever the list fills, and at the end; the waves' survivors are merged by wave 0.
-// Every valid id of a probed bucket is a candidate: no slot arithmetic (off, magic, P1) applies.  Outputs as
-// stage1_select_kernel's: K1 ascending distinct keys padded with (+inf, ANN_ID_NONE), nv_tot = valid ids seen (with
-// repeats, self included), nv_own = rows gathered.
-template <int D, bool SEG, typename RT>
-__global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *__restrict__ y, int alias,
-                                                           const u32 *__restrict__ codes,
-                                                           const unsigned char *__restrict__ pbits, int pb, u32 rpt,
-                                                           int K1, int cap, FT *__restrict__ cand_dist,
-                                                           u32 *__restrict__ cand_id, u32 *__restrict__ nv_tot,
-                                                           u32 *__restrict__ nv_own) {
+//   A) SEG: segment word of each run's bucket -> the owned ids into the wave's LDS list.  Admit::ALWAYS: prefix sum and
+//      balanced copy, no test; otherwise the concatenation of the runs' segments, 64 ids at a time through adm(),
+//      ballot-compacted: a row that is not admitted is never fetched.
+//      !SEG (a table without the sorted-prefix layout): every slot of the run's bucket row, ballot-compacted.  With
+//      Admit::ALWAYS the aliased query itself is not listed; otherwise it is listed when admitted, as in the segment
+//      path, and probe_gather drops it -- nv_own differs accordingly.
+//   B) the gather whenever the list fills, and at the end; the waves' survivors are merged by wave 0.
+// Every valid id of a probed bucket is a candidate: no slot arithmetic (off, magic, P1) applies.  pb = 0 with
+// rpt = 1 + ds gives the plain buckets of fixed mode.  tau0: the selection's initial admission threshold (key_max(), or
+// the query's radius).  Outputs as stage1_select_kernel's: K1 ascending distinct keys padded with (+inf, ANN_ID_NONE),
+// nv_tot = valid ids seen (with repeats, self included), nv_own = ids in the list = rows gathered.
+//
+// LDS carve-up, also of stage1_filter_kernel and stage1_radius_kernel (host mirror: stage1_probe_lds_bytes):
+//   Key kbuf[W][cap], kout[W][K1], mbuf[W][K1];  TryInfo tries[T];  u32 *rptr[W][64];  u32 list[W][ANN_S1_CHUNK],
+//   pref[W][64], qcode[T];  int mcnt[W];  u32 cnts[4];  u8 qbits[T][pb];  16-byte boundary;  generic d only: FT yq[d],
+//   scratch[W][d]
+template <int D, bool SEG, typename RT, typename Admit>
+__device__ __forceinline__ void stage1_fixed_body(const QParams &P, const FT *y, int alias, const u32 *codes,
+                                                  const unsigned char *pbits, int pb, u32 rpt, const Admit &adm, Key tau0,
+                                                  int K1, int cap, FT *cand_dist, u32 *cand_id, u32 *nv_tot, u32 *nv_own) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  // ---- LDS carve-up (mirrored by stage1_probe_lds_bytes on the host)
   unsigned char *sp = smem;
   Key *kbuf_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * cap;
   Key *kout_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * K1;
@@ -311,22 +399,11 @@ __global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *
 
   SelState S;
   S.kbuf = kbuf_all + (size_t)w * cap, S.kout = kout_all + (size_t)w * K1;
-  S.kcnt = 0, S.K1 = K1, S.cap = cap, S.tau = key_max();
+  S.kcnt = 0, S.K1 = K1, S.cap = cap, S.tau = tau0;
   FT *scratch = yq + (size_t)(1 + w) * P.d;
   u32 vtot = 0, vown = 0;
-
-  // the query row, as this lane's slice
   VT a[RowChunks<D>::C];
-  if constexpr (D > 0) {
-    typedef RowLay<D> L;
-    const VT *yp = reinterpret_cast<const VT *>(y + (size_t)x * D) + (lane % L::LPR);
-#pragma unroll
-    for (int c = 0; c < L::C; c++) a[c] = yp[c * L::LPR];
-  } else if constexpr (D < 0 && !OcCode<D>::GEN) {
-    const OcLanes<D> ol(P.d, lane);
-#pragma unroll
-    for (int c = 0; c < OcCode<D>::C; c++) a[c] = oc_load_chunk<D, false>(y + (size_t)x * P.d, ol.p + c * ol.oc, P.d);
-  }
+  load_query_slice<D>(P, y, x, lane, a);
 
   int cnt = 0;
   const u32 runs = (u32)P.T * rpt;
@@ -353,25 +430,36 @@ __global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *
       pref[lane] = incl - c;
       rptr[lane] = src;
       wave_lds_sync();
-      for (u32 done = 0; done < total;) {  // balanced copy of `total` ids into the list, list-capacity pieces
-        const u32 take = min((u32)ANN_S1_CHUNK - (u32)cnt, total - done);
-        for (u32 e = done + lane; e < done + take; e += ANN_WAVE) {
-          int lo_ = 0, hi_ = ANN_WAVE - 1;  // last run j with pref[j] <= e (it has c_j > 0)
-          while (lo_ < hi_) {
-            const int mid = (lo_ + hi_ + 1) >> 1;
-            if (pref[mid] <= e) lo_ = mid; else hi_ = mid - 1;
+      if constexpr (Admit::ALWAYS) {
+        for (u32 done = 0; done < total;) {  // balanced copy of `total` ids into the list, list-capacity pieces
+          const u32 take = min((u32)ANN_S1_CHUNK - (u32)cnt, total - done);
+          for (u32 e = done + lane; e < done + take; e += ANN_WAVE) {
+            int lo_ = 0, hi_ = ANN_WAVE - 1;  // last run j with pref[j] <= e (it has c_j > 0)
+            while (lo_ < hi_) {
+              const int mid = (lo_ + hi_ + 1) >> 1;
+              if (pref[mid] <= e) lo_ = mid; else hi_ = mid - 1;
+            }
+            list[cnt + (e - done)] = rptr[lo_][e - pref[lo_]];
           }
-          list[cnt + (e - done)] = rptr[lo_][e - pref[lo_]];
+          cnt += take, done += take;
+          if (cnt == ANN_S1_CHUNK) list_flush<D, RT>(P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
         }
-        cnt += take, done += take;
-        if (cnt == ANN_S1_CHUNK) {
-          wave_lds_sync();
-          vown += cnt;
-          probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
-          cnt = 0;
+      } else {
+        for (u32 e0 = 0; e0 < total; e0 += ANN_WAVE) {  // the `total` ids of these runs, 64 at a time, through the test
+          const u32 e = e0 + lane;
+          u32 id = ANN_ID_NONE;
+          if (e < total) {
+            int lo_ = 0, hi_ = ANN_WAVE - 1;  // last run j with pref[j] <= e (it has c_j > 0)
+            while (lo_ < hi_) {
+              const int mid = (lo_ + hi_ + 1) >> 1;
+              if (pref[mid] <= e) lo_ = mid; else hi_ = mid - 1;
+            }
+            id = rptr[lo_][e - pref[lo_]];
+          }
+          list_push<D, RT>(id < P.n && adm(id), id, P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
         }
       }
-      wave_lds_sync();
+      wave_lds_sync();  // pref / rptr are rewritten by the next 64 runs
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) vtot += __shfl_xor(vtot, m);
@@ -385,44 +473,21 @@ __global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *
         const u32 z = z0 + lane;
         const u32 id = z < tr.pm ? row[z] : ANN_ID_NONE;
         const bool ok = id < P.n && !(alias && id == x);
-        const bool own = ok && id >= P.lo && id < P.hi;
+        bool own;
+        if constexpr (Admit::ALWAYS) own = ok && id >= P.lo && id < P.hi;
+        else own = id < P.n && id >= P.lo && id < P.hi && adm(id);
         vtot += __popcll(__ballot(ok));
-        const u64 mm = __ballot(own);
-        if (own) list[cnt + mask_rank(mm)] = id;
-        cnt += __popcll(mm);
-        if (cnt + ANN_WAVE > ANN_S1_CHUNK) {
-          wave_lds_sync();
-          vown += cnt;
-          probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
-          cnt = 0;
-        }
+        list_push<D, RT>(own, id, P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
       }
     }
   }
-  wave_lds_sync();
-  vown += cnt;
-  probe_gather<D, RT>(P, list, cnt, alias, x, a, yq, scratch, S, y + (size_t)x * P.d);
+  list_flush<D, RT>(P, list, cnt, vown, alias, x, a, yq, scratch, S, y);
 
-  // ---- this wave's survivors -> merge buffer
-  {
-    const int m = wave_select_smallest(S.kbuf, S.kcnt, K1, S.kout);
-    for (int i = lane; i < m; i += ANN_WAVE) mbuf[(size_t)w * K1 + i] = S.kout[i];
-    if (lane == 0) {
-      mcnt[w] = m;
-      atomicAdd(&cnts[0], vtot);
-      atomicAdd(&cnts[1], vown);
-    }
-  }
-  __syncthreads();
+  const int m = merge_waves(S, mbuf, mcnt, w, W, K1, [&] {
+    atomicAdd(&cnts[0], vtot);
+    atomicAdd(&cnts[1], vown);
+  });
   if (w == 0) {
-    int total = 0;
-    for (int ww = 0; ww < W; ww++) {  // cap >= W*K1 (host guarantees)
-      const int m = mcnt[ww];
-      for (int i = lane; i < m; i += ANN_WAVE) S.kbuf[total + i] = mbuf[(size_t)ww * K1 + i];
-      total += m;
-    }
-    wave_lds_sync();
-    const int m = wave_select_smallest(S.kbuf, total, K1, S.kout);
     for (int i = lane; i < K1; i += ANN_WAVE) {
       cand_dist[(size_t)x * K1 + i] = i < m ? key_dist(S.kout[i]) : ft_inf();
       cand_id[(size_t)x * K1 + i] = i < m ? key_id(S.kout[i]) : ANN_ID_NONE;
@@ -432,4 +497,16 @@ __global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *
       nv_own[x] = cnts[1];
     }
   }
+}
+
+// Fixed mode with pair bits: every valid id of the probed buckets.
+template <int D, bool SEG, typename RT>
+__global__ __launch_bounds__(256) void stage1_probe_kernel(QParams P, const FT *__restrict__ y, int alias,
+                                                           const u32 *__restrict__ codes,
+                                                           const unsigned char *__restrict__ pbits, int pb, u32 rpt,
+                                                           int K1, int cap, FT *__restrict__ cand_dist,
+                                                           u32 *__restrict__ cand_id, u32 *__restrict__ nv_tot,
+                                                           u32 *__restrict__ nv_own) {
+  stage1_fixed_body<D, SEG, RT>(P, y, alias, codes, pbits, pb, rpt, AdmitAll{}, key_max(), K1, cap, cand_dist, cand_id, nv_tot,
+                                nv_own);
 }

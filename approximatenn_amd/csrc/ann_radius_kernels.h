@@ -5,8 +5,9 @@
 // negative or NaN radius puts nothing in range, +inf puts every row in range (a row whose distance overflowed to +inf
 // included).  A radius query returns the kcap smallest (distance, id) keys among the in-range candidates of fixed mode.
 //
-//   stage1_radius    stage1_tag_kernel's structure, both forms (segment walk, slot scan), with two changes:
-//                    - validity sits behind nullable pointers as in stage2_kq_kernel: `bits` (the allow list) and `tags`
+//   stage1_radius    stage1_fixed_body's tested form (ann_probe_kernels.h), both forms (segment walk, slot scan), as a
+//                    copy of its own, with:
+//                    - validity behind nullable pointers as in stage2_kq_kernel: `bits` (the allow list) and `tags`
 //                      may each be NULL.  NULL or not is a kernel argument, hence one wave-uniform branch each and no
 //                      template axis: one family serves plain, probe, allow list and tags.
 //                    - the admission threshold S.tau starts at the query's radius, not at key_max(): only in-range keys
@@ -18,7 +19,7 @@
 // Stage 2 and the tail merges stay the k-per-call kernels (ann_kq_kernels.h, ann_tail*_kernels.h): their input holds
 // in-range results and pads only, every key they add that is beyond the radius sorts behind every key within it, and the
 // trim cuts the row there -- the kcap smallest of a superset, trimmed, are the kcap smallest of the in-range subset.
-// QParams and the existing kernels are not touched; no call but the radius entry points launches anything from this file.
+// No call but the radius entry points launches anything from this file.
 #pragma once
 #include "ann_kq_kernels.h"
 
@@ -41,8 +42,9 @@ __device__ __forceinline__ Key radius_tau(FT r) {
 }
 
 // ------------------------------------------------------------------------------------------ stage 1
-// Same LDS carve-up as stage1_tag_kernel (stage1_probe_lds_bytes on the host); probe_gather, the selection state, the
-// merge and the outputs unchanged.  pb = 0 with rpt = 1 + ds gives the plain buckets of fixed mode.  nv_own = ids in the
+// stage1_fixed_body's tested form (ann_probe_kernels.h) kept as a copy of its own, like stage1_filter_kernel and for the
+// same reason: two f64 instances lose a wave per SIMD through the shared body (profiles/fixed_body_devcode.md).  Same LDS
+// carve-up (stage1_probe_lds_bytes on the host); probe_gather, the selection state, the merge and the outputs unchanged.  pb = 0 with rpt = 1 + ds gives the plain buckets of fixed mode.  nv_own = ids in the
 // list = rows gathered = the valid ids of the probed buckets (the radius is known only after a row is fetched).
 template <int D, bool SEG, typename RT>
 __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT *__restrict__ y, int alias,
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT 
                                                             u32 *__restrict__ nv_own) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  // ---- LDS carve-up: stage1_probe_kernel's (stage1_probe_lds_bytes on the host)
+  // ---- LDS carve-up: stage1_fixed_body's (stage1_probe_lds_bytes on the host)
   unsigned char *sp = smem;
   Key *kbuf_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * cap;
   Key *kout_all = reinterpret_cast<Key *>(sp);           sp += sizeof(Key) * (size_t)W * K1;

@@ -129,6 +129,8 @@ def load(prec="f32"):
     lib.annhip_index_set_prune.argtypes = [vp, C.c_int]
     lib.annhip_index_prune.restype = C.c_int
     lib.annhip_index_prune.argtypes = [vp]
+    lib.annhip_index_prune_bound.restype = C.c_int
+    lib.annhip_index_prune_bound.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.annhip_index_export.argtypes = [vp, C.POINTER(SaveT)]
     lib.annhip_index_reshard.argtypes = [vp, vp, sz, sz]
     lib.annhip_save_write.restype = C.c_int
@@ -233,7 +235,7 @@ def load(prec="f32"):
 # every symbol include/*.h declares for the backend library (checked by tests/test_abi.py)
 EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp_gpu", "annhip_precision", "annhip_layout_code",
             "annhip_index_create", "annhip_index_destroy", "annhip_index_info", "annhip_index_set_stream", "annhip_index_set_gather_pieces", "annhip_index_set_gather_slots", "annhip_index_set_fixed",
-            "annhip_index_set_rows", "annhip_index_rows", "annhip_index_set_prune", "annhip_index_prune",
+            "annhip_index_set_rows", "annhip_index_rows", "annhip_index_set_prune", "annhip_index_prune", "annhip_index_prune_bound",
             "annhip_index_set_probe", "annhip_index_probe", "annhip_probe_bits",
             "annhip_index_set_filter", "annhip_index_filter_count", "annhip_filter_pack", "annhip_exact_knn_filtered",
             "annhip_index_set_tags", "annhip_index_has_tags", "annhip_query_tagged", "annhip_exact_knn_tagged",

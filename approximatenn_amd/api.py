@@ -765,6 +765,16 @@ class Index:
         """annhip_index_prune: True while this index's parity-mode queries take the pruned stage 1."""
         return bool(self.lib.annhip_index_prune(self.h))
 
+    @property
+    def prune_bound(self):
+        """annhip_index_prune_bound: (E, keys) -- the certificate's E >= max ||p - binary16(p)||_2 and the K' keys the
+        preselection keeps, as the last set_prune (or the auto rule) fixed them -- or None while the index holds no
+        narrow copy and bound.  Read-only."""
+        E, keys = C.c_double(), C.c_int()
+        if not self.lib.annhip_index_prune_bound(self.h, C.byref(E), C.byref(keys)):
+            return None
+        return float(E.value), int(keys.value)
+
     def workspace(self):
         """annhip_workspace_create: scratch for one in-flight batch (pass to query(ws=..., stream=...))."""
         ws = self.lib.annhip_workspace_create(self.h)

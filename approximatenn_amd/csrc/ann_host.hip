@@ -696,6 +696,12 @@ extern "C" int annhip_index_set_prune(annhip_index *ix, int mode) {
   return prune_setup(ix, mode, "annhip_index_set_prune");
 }
 extern "C" int annhip_index_prune(const annhip_index *ix) { return prune_active(ix) ? 1 : 0; }
+extern "C" int annhip_index_prune_bound(const annhip_index *ix, double *E, int *keys) {
+  if (!ix->prune_ready) return 0;
+  if (E) *E = ix->prune_E;
+  if (keys) *keys = ix->prune_kp;
+  return 1;
+}
 
 // ----------------------------------------------------------------------------- appended rows (the tail)
 // Contract: include/ann_hip.h.  Kernels: ann_tail_kernels.h.  All of it synchronous on the null stream.

@@ -256,9 +256,16 @@ int annhip_index_rows(const annhip_index *ix);
  * on stderr and nothing changed where mode 1 cannot be served (always in the f64 library) or mode is unknown.
  * annhip_index_prune() = 1 while annhip_query / annhip_query_on on this index are pruned, else 0.
  * Statistics: annhip_stats out[7] counts the uncertified queries; out[2] counts native-row equivalents of the bytes
- * requested (narrow rows / 2 + rescored rows); the stage-1 event pair brackets preselection and rescoring together. */
+ * requested (narrow rows / 2 + rescored rows); the stage-1 event pair brackets preselection and rescoring together.
+ * annhip_index_prune_bound() reads what annhip_index_set_prune (or the auto rule) fixed for this index and changes
+ * nothing: where the index holds a narrow copy and a bound it returns 1 and stores the E of the certificate in *E and
+ * the K' of the preselection in *keys (either may be NULL); otherwise -- pruning off or refused, the copy dropped by
+ * reshard or append -- it returns 0 and stores nothing.  It says what a pruned query WOULD use, whether or not queries
+ * are pruned right now (annhip_index_prune).  K' is fixed by the call that made the bound (ANN_HIP_PRUNE_K is read then,
+ * not by a query). */
 int annhip_index_set_prune(annhip_index *ix, int mode);
 int annhip_index_prune(const annhip_index *ix);
+int annhip_index_prune_bound(const annhip_index *ix, double *E, int *keys);
 /* Point-shard an index that was built from all n rows: from now on this device owns rows [row_lo,row_hi) only
  * and reads them from shard_points_dev (device pointer to those rows, borrowed).  Tables and graph stay. */
 void annhip_index_reshard(annhip_index *ix, const ftype *shard_points_dev, size_t row_lo, size_t row_hi);

@@ -33,6 +33,22 @@ def test_headers_and_bindings_agree():
     assert declared == set(_lib.EXPORTED), declared ^ set(_lib.EXPORTED)
 
 
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_prune_accessors_are_exported_and_declared(prec):
+    """annhip_index_set_prune / annhip_index_prune and the read-only annhip_index_prune_bound (E and K' of the
+    certificate): in both libraries, in the binding list, in the header with the documented signature, and on Index."""
+    from approximatenn_amd.api import Index
+    lib = _lib.load(prec)
+    for sym in ("annhip_index_set_prune", "annhip_index_prune", "annhip_index_prune_bound"):
+        assert hasattr(lib, sym) and sym in _lib.EXPORTED, sym
+    assert lib.annhip_index_prune_bound.restype is C.c_int
+    assert lib.annhip_index_prune_bound.argtypes[1:] == [C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ann_hip.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+annhip_index_prune_bound\s*\(\s*const\s+annhip_index\s*\*\s*\w+\s*,\s*double\s*\*\s*\w+\s*,"
+                     r"\s*int\s*\*\s*\w+\s*\)\s*;", code)
+    assert isinstance(Index.prune_bound, property) and Index.prune_bound.fset is None
+
+
 def test_save_t_layout_matches_reference_abi():
     # ann.h:8-12: int, 4 size_t, 3 pointers, 2 pointers -> 80 bytes on LP64
     assert C.sizeof(_lib.SaveT) == 80

@@ -86,13 +86,24 @@ def test_pruned_list_sizes(d, monkeypatch):
     try:
         want = orc.query(sd, pts, y)
         ty = torch.from_numpy(np.array(y)).cuda()
-        ix.set_prune("on")
-        assert ix.prune
         for kp in (k + 1, 16, 33, 64):
+            # K' is fixed when pruning is switched on (prune_setup), not by the query: the variable is set around both
+            ix.set_prune("off")
+            _with_env(monkeypatch, {"ANN_HIP_PRUNE_K": str(kp)}, lambda: ix.set_prune("on"))
+            assert ix.prune
+            assert ix.prune_bound[1] == kp
             ix.stats(reset=True)
             got = _with_env(monkeypatch, {"ANN_HIP_PRUNE_K": str(kp)}, lambda: _np(ix.query(ty)))
             _same(got, want, "pruned d=%d K'=%d" % (d, kp))
-            assert ix.stats(reset=True)["uncertified_queries"] < Q / 2, "iid rows: the certificate should hold for most queries"
+            unc = ix.stats(reset=True)["uncertified_queries"]
+            if kp > k + 1:
+                assert unc < Q / 2, "iid rows: the certificate should hold for most queries"
+            else:
+                # K' = k + 1 (which never ran while the variable was set around the query only): tau is the largest
+                # exact distance of the same k + 1 rows whose largest narrow distance is B, and the row x that has B
+                # has sqrt(exact) >= sqrt(B) - ||x - h(x)|| >= sqrt(B) - E, while LB > tau needs sqrt(tau) below
+                # sqrt(B (1 - 2^-16)) - E: a full preselection of k + 1 keys is never certified, whatever the rows
+                assert unc == Q, "K' = k + 1: the certificate cannot hold (%d of %d refused)" % (unc, Q)
     finally:
         ix.close()
 

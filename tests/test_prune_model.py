@@ -1,7 +1,8 @@
 """CPU: the certificate of the pruned stage 1 (annhip_index_set_prune), restated in numpy on float32 data.  Whenever it
 certifies a query, the true k+1 smallest keys over ALL candidates lie inside the preselection made on the binary16 rows,
 so rescoring the preselection gives exactly them.  It must never certify wrongly; it may refuse as often as it likes,
-but the tests also pin that it is not vacuous (iid rows certify) and that it does refuse where it has to (scaled rows)."""
+but the tests also pin that it is not vacuous (iid rows certify) and that it does refuse where it has to (scaled rows).
+The last tests run the exact model of the device's decision on the trap data of the GPU tests (tests/prune_model.py)."""
 import numpy as np
 import pytest
 
@@ -81,3 +82,48 @@ def test_too_few_candidates_is_certified_and_odd_values_fail_safe():
     with np.errstate(over="ignore"):
         big = np.full((4, 8), 1e6, dtype=np.float32)
     assert M.row_error(big) == np.inf                # overflows binary16: no bound, never eligible
+
+
+@pytest.mark.parametrize("d", [64, 80])
+def test_exact_model_on_trap_data(d):
+    """The exact model (DeviceModel: the device's candidates, distance bits and order) on the trap data the GPU tests
+    use.  trap_case asserts the conditions on the inputs: at least 3 queries whose rescored preselection is not the
+    truth, none of them certified, both outcomes, no decision within 2^-30 of flipping, and three different certified
+    counts at E, E / 2 and 2 E.  With E = 0 the same model certifies wrong answers: these inputs tell a broken bound
+    from a sound one, which iid rows never do."""
+    k = 10
+    c, dec = M.trap_case(3000, d, k, 3, 192, seed=M.MAIN_SEED[d], three_counts=True)
+    kp = M.default_keys(k)
+    broken = c.model.decide(c.cands, kp, 0.0)
+    assert broken.wrong >= 1, "E = 0 must certify a wrong answer on these data (%r)" % broken
+    assert np.array_equal(broken.trap, dec.trap), "what the preselection holds does not depend on E"
+    counts = [int(c.model.decide(c.cands, kp, e).certified.sum()) for e in (0.0, c.E / 2, c.E, 2 * c.E, 1e3)]
+    assert counts == sorted(counts, reverse=True) and counts[-1] < counts[0], "a larger E certifies no more: %s" % counts
+    # the sizes of the list: at K' = k + 1 the certificate can hold only where B > tau by the margin, and more keys can
+    # only shrink the set of traps
+    traps = [int(c.model.decide(c.cands, q, c.E).trap.sum()) for q in (k + 1, 16, 33, 64)]
+    assert traps == sorted(traps, reverse=True) and traps[0] > traps[-1], traps
+    for q in (k + 1, 16, 33, 64):
+        assert c.model.decide(c.cands, q, c.E).wrong == 0
+    # K' = k + 1: the row that has B is among the k + 1 rescored rows, and its exact distance alone keeps tau above LB
+    assert not c.model.decide(c.cands, k + 1, c.E).certified.any()
+
+
+def test_exact_model_is_the_stage1_of_the_cpu_engine():
+    """The model's truth -- the k+1 smallest keys over the distinct valid candidates, on the numpy tree -- against
+    CpuShardEngine.stage1_local, which computes every distance through the oracle's own tree: same ids, same bits."""
+    import torch
+    c, _ = M.trap_case(3000, 64, 10, 3, 192, seed=M.MAIN_SEED[64], three_counts=True)
+    m, K1, qs = c.model, c.k + 1, 12
+    y = np.array(c.y[:qs])
+    codes = torch.from_numpy(m.eng.orc.query_codes(m.eng.hs, y).astype(np.uint32).view(np.int32).copy())
+    cd, ci, _ = m.eng.stage1_local(torch.from_numpy(y), False, codes)
+    for x, (ids, dh, dx) in enumerate(m.gather(y)):
+        o = M.keys_sorted(dx, ids)[:K1]
+        assert np.array_equal(ids[o], ci.numpy().view(np.uint32)[x])
+        assert np.array_equal(dx[o].view(np.uint32), cd.numpy().view(np.uint32)[x])
+
+
+def test_keys_clamp():
+    assert [M.clamp_keys(10, a) for a in (0, 11, 16, 33, 64, 200, 5)] == [16, 11, 16, 33, 64, 64, 11]
+    assert M.clamp_keys(31, 0) == 48 and M.clamp_keys(1, 0) == 16

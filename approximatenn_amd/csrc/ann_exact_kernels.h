@@ -11,6 +11,12 @@
 // current k-th best key is dropped with one compare; survivors go to a per-query LDS buffer owned by the wave (no
 // workgroup synchronisation in the selection) that is compacted to the k best when it fills.  Every (query, range)
 // leaves its k best keys, ascending, in the workspace; exact_merge_kernel merges the ranges of a query.
+//
+// One family for every form of the scan: exact_scan_kernel<D, V> for the register layouts and exact_scan_generic_kernel<V>
+// for any d, V (ExValid) saying where a row's validity comes from -- nothing (annhip_exact_knn), a bit of the allow list
+// (annhip_exact_knn_filtered), or a tag word plus an optional bit (annhip_exact_knn_tagged).  The lines that differ are
+// chosen with `if constexpr`: an instance holds no line of another form, and compiles to the code of a kernel written for
+// that form alone (profiles/exact_scan_fold_devcode.md).
 #pragma once
 #include "ann_query_kernels.h"
 
@@ -177,8 +183,58 @@ __device__ __forceinline__ void ex_fill_tile(FT *tile, const FT *points, u32 t0,
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs A) {
+// ------------------------------------------------------------------------------------------ validity
+// Which rows compete.  The values are what exact_shape()'s argument means on the host; the tail's kernels
+// (ann_tail_kernels.h, ann_tail_hash_kernels.h) take the same enum.
+enum ExValid { EX_ALL = 0, EX_BITS = 1, EX_TAGS = 2 };  // EX_TAGS: the tag test, and the allow list where bits != NULL
+
+// EX_BITS: one bit of the allow list (ann_filter_kernels.h) for every row of a tile: the bitmap words that cover rows
+// [t0, t0 + rows) sit in LDS from word t0 >> 5 on -- fetched once per tile, read by every wave for all its queries.
+#define ANN_EX_TBITS(tile_rows) ((size_t)(tile_rows) / 32 + 2)  // words of LDS behind the waves' buffers
+__device__ __forceinline__ u32 ex_tile_words(u32 t0, u32 rows) { return ((t0 + rows - 1) >> 5) - (t0 >> 5) + 1; }
+__device__ __forceinline__ bool ex_tile_allows(const u32 *tbits, u32 t0, u32 id) {
+  return (tbits[(id >> 5) - (t0 >> 5)] >> (id & 31u)) & 1u;
+}
+
+// EX_TAGS: one tag word (ann_tag_kernels.h) for every row of a tile: ttags[r] = tags[t0 + r], A.tile_rows words of LDS
+// behind the waves' buffers, then the ANN_EX_TBITS words of the allow list (used only where bits != NULL).  Host mirror:
+// exact_shape's smem_of.
+struct ExValidArgs {
+  const u32 *tags, *bits;  // EX_BITS: bits (read through the kernels' `allow`); EX_TAGS: tags, and bits or NULL
+  const u32 *qmask, *qvalue;
+};
+
+// the validity words of tile [t0, t0 + rows) -> LDS.  A macro: the kernels' loops as they stand, not an inlined function
+// (which moved registers in the unaligned layouts' EX_BITS kernels).  Names of the enclosing kernel: V, tags, bits, ttags, tbits.
+#define ANN_EX_FILL_WORDS(t0, rows)                                                                            \
+  {                                                                                                            \
+    if constexpr (V == EX_TAGS)                                                                                \
+      for (u32 i = threadIdx.x; i < (rows); i += blockDim.x) ttags[i] = tags[(t0) + i];                        \
+    if constexpr (V != EX_ALL)                                                                                 \
+      if (V == EX_BITS || bits)                                                                                \
+        for (u32 i = threadIdx.x; i < ex_tile_words(t0, rows); i += blockDim.x) tbits[i] = bits[((t0) >> 5) + i]; \
+  }
+
+// ------------------------------------------------------------------------------------------ the scan
+// EX_BITS: a row whose bit is clear is never a survivor, and a wave pass without an allowed row is not scored at all.
+// Where the next tile travels through registers, so does its bitmap: one word per thread (such a tile has at most 128
+// rows per wave, hence fewer words than the workgroup has threads).
+// EX_TAGS: each of the wave's ANN_EX_QB queries applies its own (mask, value) in pass[i]; a wave pass in which no row
+// matches any of the four is not scored at all.  Where the next tile travels through registers, so do its tags: one word
+// per thread (the host prefetches only where a tile has no more rows than the workgroup has threads, i.e. rows of 32
+// bytes at least).  That word takes the place of the prefetched bitmap word -- these kernels have no register to spare
+// (168 per lane with 12 waves) -- so where an allow list is given TOO, its words for the next tile are fetched after the
+// current one is scored, latency exposed.  The tag word is read from LDS twice per wave pass (before the row loads for
+// the skip, after the reduction for pass[i]) rather than kept live across the reduction.
+// The allow list reaches the kernel twice: EX_BITS reads it through `allow`, a __restrict__ kernel argument of its own,
+// EX_TAGS through G.bits like its tags.  The compiler treats the two differently (only the former is `noalias`), and
+// each form's code is what it is with its own: with `allow` the tagged kernels grow by five instructions, with G.bits
+// the allow-list kernels of the layouts that do not prefetch change.  The host passes the same pointer in both.
+// tail_merge_kernel (ann_tail_kernels.h) is this loop once more, seeded from a result row and without row ranges: it
+// stays a kernel of its own, since a body shared through a function does not compile to the same code
+// (profiles/fixed_body_devcode.md).
+template <int D, int V>
+__global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs A, ExValidArgs G, const u32 *__restrict__ allow) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int C = RowChunks<D>::C;
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
@@ -186,16 +242,26 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
   FT *tile = reinterpret_cast<FT *>(smem);
   const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
   Key *kbase = reinterpret_cast<Key *>(smem + tile_bytes) + (size_t)w * ((size_t)ANN_EX_QB * A.cap + A.k);
+  u32 *ttags = reinterpret_cast<u32 *>(smem + tile_bytes + (size_t)W * sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k));
+  u32 *tbits = V == EX_TAGS ? ttags + A.tile_rows : ttags;
+  const u32 *__restrict__ tags = G.tags, *__restrict__ bits = V == EX_BITS ? allow : G.bits;
   const u32 qrel = (blockIdx.x * W + w) * ANN_EX_QB;  // first query of this wave, relative to q0
   const u32 qbase = A.q0 + qrel, qend = A.q0 + A.qn;
   ExSel S;
   S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
   const ExLanes<D> ln(d, lane);
   VT a[ANN_EX_QB][C];
+  u32 qm[ANN_EX_QB], qv[ANN_EX_QB];  // wave-uniform: scalar registers
 #pragma unroll
   for (int i = 0; i < ANN_EX_QB; i++) {
     const u32 q = qbase + i < qend ? qbase + i : qend - 1;  // loads stay inside y; the result is never admitted
     const FT *yq = A.y + (size_t)q * d;
+    if constexpr (V == EX_TAGS) {
+      const u32 qu = __builtin_amdgcn_readfirstlane(q);  // (the wave index is uniform, which the compiler cannot see)
+      qm[i] = G.qmask[qu], qv[i] = G.qvalue[qu];         // scalar loads into scalar registers
+    } else {
+      qm[i] = 0, qv[i] = 0;
+    }
 #pragma unroll
     for (int c = 0; c < C; c++) {
       if constexpr (D > 0) a[i][c] = reinterpret_cast<const VT *>(yq)[ln.p + c * ln.oc];
@@ -206,28 +272,43 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
   const u32 r_begin = blockIdx.y * A.range_rows;
   const u32 r_end = min(A.n, r_begin + A.range_rows);
   u32 t0 = r_begin, rows = r_begin < r_end ? min((u32)A.tile_rows, r_end - r_begin) : 0;
-  if (rows) ex_fill_tile(tile, A.points, t0, rows, d);
+  if (rows) {
+    ex_fill_tile(tile, A.points, t0, rows, d);
+    ANN_EX_FILL_WORDS(t0, rows)
+  }
   // The queries have arrived before the loop starts (s_waitcnt vmcnt(0)).  Otherwise the waits for them sit in the first
   // row pass of EVERY tile, where vmcnt counts the prefetched pieces of the next tile as well and waits those out too.
   __builtin_amdgcn_s_waitcnt(0x0F70);
   while (rows) {
-    __syncthreads();  // the tile is in LDS
+    __syncthreads();  // the tile and its validity words are in LDS
     const u32 t1 = t0 + rows;
     const u32 rows1 = t1 < r_end ? min((u32)A.tile_rows, r_end - t1) : 0;
     // the next tile's loads are in flight while this one is scored
     typedef FT pf_t __attribute__((ext_vector_type(ANN_VEC)));
     pf_t pf0 = 0, pf1 = 0;
+    u32 pfw = 0;  // EX_BITS: the next tile's bitmap word of this thread; EX_TAGS: its tag word
     if constexpr (ExCfg<D>::PREFETCH) {
       if (prefetch && rows1) {  // unconditional loads from clamped addresses: plain registers, nothing waits here
         const pf_t *src = reinterpret_cast<const pf_t *>(A.points + (size_t)t1 * d);
         const u32 last = rows1 * (u32)(d / ANN_VEC) - 1;
         pf0 = src[min(threadIdx.x, last)];
         pf1 = src[min(threadIdx.x + blockDim.x, last)];
+        if constexpr (V == EX_BITS) pfw = bits[(t1 >> 5) + min(threadIdx.x, ex_tile_words(t1, rows1) - 1)];
+        if constexpr (V == EX_TAGS) pfw = tags[t1 + min(threadIdx.x, rows1 - 1)];
       }
     }
     for (u32 r0 = 0; r0 < rows; r0 += ln.rpw) {
       const u32 r = r0 + ln.g;
       const bool act = ln.valid && r < rows;
+      bool allowed = act;
+      if constexpr (V != EX_ALL) {
+        allowed = act && ((V == EX_TAGS && !bits) || ex_tile_allows(tbits, t0, t0 + r));
+        if constexpr (V == EX_TAGS) {
+          const u32 tg = ttags[act ? r : r0];
+          allowed = allowed && ((tg & qm[0]) == qv[0] || (tg & qm[1]) == qv[1] || (tg & qm[2]) == qv[2] || (tg & qm[3]) == qv[3]);
+        }
+        if (!__ballot(allowed)) continue;  // wave-uniform: no row of this pass can survive for any of the four queries
+      }
       const FT *rp = tile + (size_t)(act ? r : r0) * d;
       VT b[C];
 #pragma unroll
@@ -236,14 +317,20 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
         else b[c] = oc_load_chunk<D, false>(rp, ln.p + c * ln.oc, d);
       }
       const u32 id = t0 + r;
-      const bool head = act && ln.p == 0;
+      const bool head = allowed && ln.p == 0;
       // all four trees first (independent chains the scheduler interleaves), then ONE branch for the rare survivors
       Key key[ANN_EX_QB];
       bool pass[ANN_EX_QB];
 #pragma unroll
       for (int i = 0; i < ANN_EX_QB; i++) key[i] = key_make(ex_reduce<D>(a[i], b, ln.oc, ln.p, d), id);
+      u32 tg = 0;
+      if constexpr (V == EX_TAGS) {
+        asm volatile("" ::: "memory");  // a second LDS read, not a register kept through the reduction
+        tg = ttags[act ? r : r0];
+      }
 #pragma unroll
-      for (int i = 0; i < ANN_EX_QB; i++) pass[i] = head && key_less(key[i], S.tau[i]) && !(A.self && id == qbase + i);
+      for (int i = 0; i < ANN_EX_QB; i++)
+        pass[i] = head && (V != EX_TAGS || (tg & qm[i]) == qv[i]) && key_less(key[i], S.tau[i]) && !(A.self && id == qbase + i);
       if (__ballot(pass[0] || pass[1] || pass[2] || pass[3])) {
         S.offer<0>(pass[0], key[0]);
         S.offer<1>(pass[1], key[1]);
@@ -260,10 +347,20 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
         const u32 pieces = rows1 * (u32)(d / ANN_VEC);
         if (threadIdx.x < pieces) t[threadIdx.x] = pf0;
         if (threadIdx.x + blockDim.x < pieces) t[threadIdx.x + blockDim.x] = pf1;
+        if constexpr (V == EX_BITS) {
+          if (threadIdx.x < ex_tile_words(t1, rows1)) tbits[threadIdx.x] = pfw;
+        }
+        if constexpr (V == EX_TAGS) {
+          if (threadIdx.x < rows1) ttags[threadIdx.x] = pfw;  // (rows1 <= blockDim.x: exact_shape)
+          if (bits && threadIdx.x < ex_tile_words(t1, rows1)) tbits[threadIdx.x] = bits[(t1 >> 5) + threadIdx.x];
+        }
         stored = true;
       }
     }
-    if (!stored) ex_fill_tile(tile, A.points, t1, rows1, d);
+    if (!stored) {
+      ex_fill_tile(tile, A.points, t1, rows1, d);
+      ANN_EX_FILL_WORDS(t1, rows1)
+    }
     t0 = t1, rows = rows1;
   }
   S.store(A.ws, qrel, A.qn, A.ranges, (int)blockIdx.y);
@@ -273,37 +370,16 @@ static_assert(ANN_EX_QB == 4 && ANN_EX_PF == 2, "exact_scan_kernel names its fou
 // Any d without a register layout: the literal in-place tree through LDS, several (query, row) pairs of a wave at once.
 // Lanes are spread over pair x z (z padded to a power of two: no division), so one fence per tree level serves
 // npairs pairs.  A wave takes its ANN_EX_QB queries one after another over each tile (the query sits in LDS).
-__global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void exact_scan_generic_kernel(ExArgs A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int d = A.d;
-  int NP = ANN_EX_GEN_ELEMS / d;
-  NP = NP < 1 ? 1 : (NP > ANN_WAVE ? ANN_WAVE : NP);
-  FT *tile = reinterpret_cast<FT *>(smem);
-  const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
-  const size_t wave_ft = ((size_t)(1 + NP) * d * sizeof(FT) + 15) & ~(size_t)15;  // yq[d], m[NP][d]
-  const size_t wave_bytes = wave_ft + sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k);
-  unsigned char *wb = smem + tile_bytes + (size_t)w * wave_bytes;
-  FT *yq = reinterpret_cast<FT *>(wb), *m = yq + d;
-  Key *kbase = reinterpret_cast<Key *>(wb + wave_ft);
-  const u32 qrel = (blockIdx.x * W + w) * ANN_EX_QB;
-  const u32 qbase = A.q0 + qrel, qend = A.q0 + A.qn;
-  ExSel S;
-  S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
-  int sh0 = 0;  // d <= 1 << sh0
-  while ((1 << sh0) < d) sh0++;
-  const FT zero = 0;
-  const u32 r_begin = blockIdx.y * A.range_rows;
-  const u32 r_end = min(A.n, r_begin + A.range_rows);
-  for (u32 t0 = r_begin; t0 < r_end; t0 += A.tile_rows) {
-    const u32 rows = min((u32)A.tile_rows, r_end - t0);
-    __syncthreads();
-    ex_fill_tile(tile, A.points, t0, rows, d);
-    __syncthreads();
-#define ANN_EX_GEN_QUERY(I)                                                                                  \
-  if (qbase + (I) < qend) {                                                                                  \
+//
+// ANN_EX_GEN_QUERY(q, select): query q of A.y over the rows of the tile, NP at a time.  The distance part -- the query
+// into yq, the squared differences into m, the tree in place -- is the one text of the literal tree for this kernel and
+// for tail_merge_generic_kernel; `select` are the statements that follow it for every batch, where m[lane * d] holds the
+// distance of row r0 + lane (lane < np): they make the key, fence (m is rewritten by the next batch) and offer it.
+// Names of the enclosing kernel: A, lane, d, rows, NP, sh0, zero, tile, yq, m.
+#define ANN_EX_GEN_QUERY(q, ...)                                                                             \
+  {                                                                                                          \
     wave_lds_sync();                                                                                         \
-    for (int z = lane; z < d; z += ANN_WAVE) yq[z] = A.y[(size_t)(qbase + (I)) * d + z];                     \
+    for (int z = lane; z < d; z += ANN_WAVE) yq[z] = A.y[(size_t)(q) * d + z];                               \
     wave_lds_sync();                                                                                         \
     for (u32 r0 = 0; r0 < rows; r0 += NP) {                                                                  \
       const int np = (int)min((u32)NP, rows - r0);                                                           \
@@ -329,15 +405,62 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void exact_scan_generic_kern
         }                                                                                                    \
         wave_lds_sync();                                                                                     \
       }                                                                                                      \
-      const bool act = lane < np;                                                                            \
+      __VA_ARGS__                                                                                            \
+    }                                                                                                        \
+  }
+
+template <int V>
+__global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void exact_scan_generic_kernel(ExArgs A, ExValidArgs G, const u32 *__restrict__ allow) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
+  const int d = A.d;
+  int NP = ANN_EX_GEN_ELEMS / d;
+  NP = NP < 1 ? 1 : (NP > ANN_WAVE ? ANN_WAVE : NP);
+  FT *tile = reinterpret_cast<FT *>(smem);
+  const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
+  const size_t wave_ft = ((size_t)(1 + NP) * d * sizeof(FT) + 15) & ~(size_t)15;  // yq[d], m[NP][d]
+  const size_t wave_bytes = wave_ft + sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k);
+  unsigned char *wb = smem + tile_bytes + (size_t)w * wave_bytes;
+  FT *yq = reinterpret_cast<FT *>(wb), *m = yq + d;
+  Key *kbase = reinterpret_cast<Key *>(wb + wave_ft);
+  u32 *ttags = reinterpret_cast<u32 *>(smem + tile_bytes + (size_t)W * wave_bytes);
+  u32 *tbits = V == EX_TAGS ? ttags + A.tile_rows : ttags;
+  const u32 *__restrict__ tags = G.tags, *__restrict__ bits = V == EX_BITS ? allow : G.bits;
+  const u32 qrel = (blockIdx.x * W + w) * ANN_EX_QB;
+  const u32 qbase = A.q0 + qrel, qend = A.q0 + A.qn;
+  ExSel S;
+  S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
+  int sh0 = 0;  // d <= 1 << sh0
+  while ((1 << sh0) < d) sh0++;
+  const FT zero = 0;
+  const u32 r_begin = blockIdx.y * A.range_rows;
+  const u32 r_end = min(A.n, r_begin + A.range_rows);
+  for (u32 t0 = r_begin; t0 < r_end; t0 += A.tile_rows) {
+    const u32 rows = min((u32)A.tile_rows, r_end - t0);
+    __syncthreads();
+    ex_fill_tile(tile, A.points, t0, rows, d);
+    ANN_EX_FILL_WORDS(t0, rows)
+    __syncthreads();
+#define ANN_EX_GEN_SCAN(I)                                                                                   \
+  if (qbase + (I) < qend) {                                                                                  \
+    const u32 qu = __builtin_amdgcn_readfirstlane(qbase + (I));                                              \
+    const u32 qm = V == EX_TAGS ? G.qmask[qu] : 0, qv = V == EX_TAGS ? G.qvalue[qu] : 0;                     \
+    ANN_EX_GEN_QUERY(qbase + (I), {                                                                          \
       const u32 id = t0 + r0 + lane;                                                                         \
+      bool act;                                                                                              \
+      if constexpr (V == EX_TAGS) {                                                                          \
+        act = lane < np && (ttags[r0 + lane] & qm) == qv && (!bits || ex_tile_allows(tbits, t0, id));        \
+      } else {                                                                                               \
+        act = lane < np;                                                                                     \
+        if constexpr (V == EX_BITS) act = act && ex_tile_allows(tbits, t0, id);                              \
+      }                                                                                                      \
       const Key key = key_make(act ? m[lane * d] : zero, id);                                                \
       wave_lds_sync(); /* m is rewritten by the next batch */                                                \
       S.offer<I>(act && key_less(key, S.tau[I]) && !(A.self && id == qbase + (I)), key);                     \
-    }                                                                                                        \
+    })                                                                                                       \
   }
-    ANN_EX_GEN_QUERY(0) ANN_EX_GEN_QUERY(1) ANN_EX_GEN_QUERY(2) ANN_EX_GEN_QUERY(3)
-#undef ANN_EX_GEN_QUERY
+    ANN_EX_GEN_SCAN(0) ANN_EX_GEN_SCAN(1) ANN_EX_GEN_SCAN(2) ANN_EX_GEN_SCAN(3)
+#undef ANN_EX_GEN_SCAN
   }
   S.store(A.ws, qrel, A.qn, A.ranges, (int)blockIdx.y);
 }
@@ -368,4 +491,11 @@ __global__ __launch_bounds__(256) void exact_merge_kernel(const Key *__restrict_
     if (lane == 0) io[j] = key_id(best), dout[j] = key_dist(best);
     prev = best;
   }
+}
+
+// exact_merge_kernel unpacks key_max() where a query has fewer than k valid rows (EX_BITS / EX_TAGS): those entries ->
+// (n, +inf)
+__global__ void exact_tail_kernel(size_t count, size_t n, size_t *__restrict__ ids, FT *__restrict__ dists) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
+    if (ids[e] == (size_t)ANN_ID_NONE) ids[e] = n, dists[e] = ft_inf();
 }

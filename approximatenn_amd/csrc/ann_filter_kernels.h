@@ -1,5 +1,5 @@
-// ann_filter_kernels.h -- allow-list row filter of the fixed query mode and of the exact scan (annhip_index_set_filter,
-// annhip_exact_knn_filtered; gfx950).
+// ann_filter_kernels.h -- allow-list row filter of the fixed query mode (annhip_index_set_filter; gfx950).  The exact scan
+// tests the same bitmap in its EX_BITS form (ann_exact_kernels.h).
 //
 // The allow list is a bitmap, u32 bits[ceil(n / 32)]: row i is allowed iff bits[i >> 5] >> (i & 31) & 1.  A filter only
 // narrows what fixed mode calls a valid id, so the kernels here are the fixed-mode kernels with one more test:
@@ -10,8 +10,6 @@
 //   stage2_fixed_body   stage2_select_kernel with the policy in its `ok` predicate: stage 2 of the filter and tag
 //                    families; stage2_filter is its entry point for the allow list
 //   filter_pack      u8 flags -> bitmap;   filter_count   popcount of bits [0, n)
-//   exact_scan_filtered / exact_scan_generic_filtered   the exact scan's two kernels with the tile's bitmap words in LDS
-//   exact_tail       the exact scan's "no row" padding -> (n, +inf)
 //
 // The bitmap is a separate kernel argument everywhere, and an unfiltered query launches nothing from this file.
 #pragma once
@@ -339,196 +337,4 @@ __global__ __launch_bounds__(256) void filter_count_kernel(size_t n, const u32 *
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
   if (lane_id() == 0 && acc) atomicAdd(out, acc);
-}
-
-// ------------------------------------------------------------------------------------------ exact scan
-// One bit of the allow list for every row of a tile: the bitmap words that cover rows [t0, t0 + rows) sit in LDS from
-// word t0 >> 5 on -- fetched once per tile, read by every wave for all its queries.
-#define ANN_EX_TBITS(tile_rows) ((size_t)(tile_rows) / 32 + 2)  // words of LDS behind the waves' buffers
-__device__ __forceinline__ u32 ex_tile_words(u32 t0, u32 rows) { return ((t0 + rows - 1) >> 5) - (t0 >> 5) + 1; }
-__device__ __forceinline__ bool ex_tile_allows(const u32 *tbits, u32 t0, u32 id) {
-  return (tbits[(id >> 5) - (t0 >> 5)] >> (id & 31u)) & 1u;
-}
-
-// exact_scan_kernel with the allow list: a row whose bit is clear is never a survivor, and a wave pass without an allowed
-// row is not scored at all.  Where the next tile travels through registers, so does its bitmap: one word per thread (such
-// a tile has at most 128 rows per wave, hence fewer words than the workgroup has threads).
-template <int D>
-__global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_filtered_kernel(ExArgs A, const u32 *__restrict__ bits) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int C = RowChunks<D>::C;
-  const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int d = A.d;
-  FT *tile = reinterpret_cast<FT *>(smem);
-  const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
-  Key *kbase = reinterpret_cast<Key *>(smem + tile_bytes) + (size_t)w * ((size_t)ANN_EX_QB * A.cap + A.k);
-  u32 *tbits = reinterpret_cast<u32 *>(smem + tile_bytes + (size_t)W * sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k));
-  const u32 qrel = (blockIdx.x * W + w) * ANN_EX_QB;  // first query of this wave, relative to q0
-  const u32 qbase = A.q0 + qrel, qend = A.q0 + A.qn;
-  ExSel S;
-  S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
-  const ExLanes<D> ln(d, lane);
-  VT a[ANN_EX_QB][C];
-#pragma unroll
-  for (int i = 0; i < ANN_EX_QB; i++) {
-    const u32 q = qbase + i < qend ? qbase + i : qend - 1;  // loads stay inside y; the result is never admitted
-    const FT *yq = A.y + (size_t)q * d;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-      if constexpr (D > 0) a[i][c] = reinterpret_cast<const VT *>(yq)[ln.p + c * ln.oc];
-      else a[i][c] = oc_load_chunk<D, false>(yq, ln.p + c * ln.oc, d);
-    }
-  }
-  const bool prefetch = ExCfg<D>::PREFETCH && A.prefetch;
-  const u32 r_begin = blockIdx.y * A.range_rows;
-  const u32 r_end = min(A.n, r_begin + A.range_rows);
-  u32 t0 = r_begin, rows = r_begin < r_end ? min((u32)A.tile_rows, r_end - r_begin) : 0;
-  if (rows) {
-    ex_fill_tile(tile, A.points, t0, rows, d);
-    for (u32 i = threadIdx.x; i < ex_tile_words(t0, rows); i += blockDim.x) tbits[i] = bits[(t0 >> 5) + i];
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // the queries have arrived before the loop starts (see exact_scan_kernel)
-  while (rows) {
-    __syncthreads();  // the tile and its bits are in LDS
-    const u32 t1 = t0 + rows;
-    const u32 rows1 = t1 < r_end ? min((u32)A.tile_rows, r_end - t1) : 0;
-    // the next tile's loads are in flight while this one is scored
-    typedef FT pf_t __attribute__((ext_vector_type(ANN_VEC)));
-    pf_t pf0 = 0, pf1 = 0;
-    u32 pfw = 0;
-    if constexpr (ExCfg<D>::PREFETCH) {
-      if (prefetch && rows1) {  // unconditional loads from clamped addresses: plain registers, nothing waits here
-        const pf_t *src = reinterpret_cast<const pf_t *>(A.points + (size_t)t1 * d);
-        const u32 last = rows1 * (u32)(d / ANN_VEC) - 1;
-        pf0 = src[min(threadIdx.x, last)];
-        pf1 = src[min(threadIdx.x + blockDim.x, last)];
-        pfw = bits[(t1 >> 5) + min(threadIdx.x, ex_tile_words(t1, rows1) - 1)];
-      }
-    }
-    for (u32 r0 = 0; r0 < rows; r0 += ln.rpw) {
-      const u32 r = r0 + ln.g;
-      const bool act = ln.valid && r < rows;
-      const bool allowed = act && ex_tile_allows(tbits, t0, t0 + r);
-      if (!__ballot(allowed)) continue;  // wave-uniform: no row of this pass can survive
-      const FT *rp = tile + (size_t)(act ? r : r0) * d;
-      VT b[C];
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        if constexpr (D > 0) b[c] = reinterpret_cast<const VT *>(rp)[ln.p + c * ln.oc];
-        else b[c] = oc_load_chunk<D, false>(rp, ln.p + c * ln.oc, d);
-      }
-      const u32 id = t0 + r;
-      const bool head = allowed && ln.p == 0;
-      Key key[ANN_EX_QB];
-      bool pass[ANN_EX_QB];
-#pragma unroll
-      for (int i = 0; i < ANN_EX_QB; i++) key[i] = key_make(ex_reduce<D>(a[i], b, ln.oc, ln.p, d), id);
-#pragma unroll
-      for (int i = 0; i < ANN_EX_QB; i++) pass[i] = head && key_less(key[i], S.tau[i]) && !(A.self && id == qbase + i);
-      if (__ballot(pass[0] || pass[1] || pass[2] || pass[3])) {
-        S.offer<0>(pass[0], key[0]);
-        S.offer<1>(pass[1], key[1]);
-        S.offer<2>(pass[2], key[2]);
-        S.offer<3>(pass[3], key[3]);
-      }
-    }
-    if (!rows1) break;
-    __syncthreads();  // every wave has read the tile
-    bool stored = false;
-    if constexpr (ExCfg<D>::PREFETCH) {
-      if (prefetch) {
-        pf_t *t = reinterpret_cast<pf_t *>(tile);
-        const u32 pieces = rows1 * (u32)(d / ANN_VEC);
-        if (threadIdx.x < pieces) t[threadIdx.x] = pf0;
-        if (threadIdx.x + blockDim.x < pieces) t[threadIdx.x + blockDim.x] = pf1;
-        if (threadIdx.x < ex_tile_words(t1, rows1)) tbits[threadIdx.x] = pfw;
-        stored = true;
-      }
-    }
-    if (!stored) {
-      ex_fill_tile(tile, A.points, t1, rows1, d);
-      for (u32 i = threadIdx.x; i < ex_tile_words(t1, rows1); i += blockDim.x) tbits[i] = bits[(t1 >> 5) + i];
-    }
-    t0 = t1, rows = rows1;
-  }
-  S.store(A.ws, qrel, A.qn, A.ranges, (int)blockIdx.y);
-}
-
-// exact_scan_generic_kernel with the allow list
-__global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void exact_scan_generic_filtered_kernel(ExArgs A,
-                                                                                           const u32 *__restrict__ bits) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int d = A.d;
-  int NP = ANN_EX_GEN_ELEMS / d;
-  NP = NP < 1 ? 1 : (NP > ANN_WAVE ? ANN_WAVE : NP);
-  FT *tile = reinterpret_cast<FT *>(smem);
-  const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
-  const size_t wave_ft = ((size_t)(1 + NP) * d * sizeof(FT) + 15) & ~(size_t)15;  // yq[d], m[NP][d]
-  const size_t wave_bytes = wave_ft + sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k);
-  unsigned char *wb = smem + tile_bytes + (size_t)w * wave_bytes;
-  FT *yq = reinterpret_cast<FT *>(wb), *m = yq + d;
-  Key *kbase = reinterpret_cast<Key *>(wb + wave_ft);
-  u32 *tbits = reinterpret_cast<u32 *>(smem + tile_bytes + (size_t)W * wave_bytes);
-  const u32 qrel = (blockIdx.x * W + w) * ANN_EX_QB;
-  const u32 qbase = A.q0 + qrel, qend = A.q0 + A.qn;
-  ExSel S;
-  S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
-  int sh0 = 0;  // d <= 1 << sh0
-  while ((1 << sh0) < d) sh0++;
-  const FT zero = 0;
-  const u32 r_begin = blockIdx.y * A.range_rows;
-  const u32 r_end = min(A.n, r_begin + A.range_rows);
-  for (u32 t0 = r_begin; t0 < r_end; t0 += A.tile_rows) {
-    const u32 rows = min((u32)A.tile_rows, r_end - t0);
-    __syncthreads();
-    ex_fill_tile(tile, A.points, t0, rows, d);
-    for (u32 i = threadIdx.x; i < ex_tile_words(t0, rows); i += blockDim.x) tbits[i] = bits[(t0 >> 5) + i];
-    __syncthreads();
-#define ANN_EX_GEN_QUERY(I)                                                                                  \
-  if (qbase + (I) < qend) {                                                                                  \
-    wave_lds_sync();                                                                                         \
-    for (int z = lane; z < d; z += ANN_WAVE) yq[z] = A.y[(size_t)(qbase + (I)) * d + z];                     \
-    wave_lds_sync();                                                                                         \
-    for (u32 r0 = 0; r0 < rows; r0 += NP) {                                                                  \
-      const int np = (int)min((u32)NP, rows - r0);                                                           \
-      for (int it = lane; it < (np << sh0); it += ANN_WAVE) {                                                \
-        const int pr = it >> sh0, z = it & ((1 << sh0) - 1);                                                 \
-        if (z < d) {                                                                                         \
-          const FT df = yq[z] - tile[(size_t)(r0 + pr) * d + z];                                             \
-          m[pr * d + z] = df * df;                                                                           \
-        }                                                                                                    \
-      }                                                                                                      \
-      wave_lds_sync();                                                                                       \
-      int sh = sh0;                                                                                          \
-      for (int s = d; s >> 1; s >>= 1) {                                                                     \
-        const int h = s >> 1;                                                                                \
-        while (sh > 0 && (1 << (sh - 1)) >= h) sh--; /* h <= 1 << sh */                                      \
-        for (int it = lane; it < (np << sh); it += ANN_WAVE) {                                               \
-          const int pr = it >> sh, z = it & ((1 << sh) - 1);                                                 \
-          if (z < h) {                                                                                       \
-            FT *mp = m + pr * d;                                                                             \
-            const FT g = ((s & 1) && z == 0) ? mp[s - 1] : zero;                                             \
-            mp[z] = mp[z] + (mp[z + h] + g);                                                                 \
-          }                                                                                                  \
-        }                                                                                                    \
-        wave_lds_sync();                                                                                     \
-      }                                                                                                      \
-      const u32 id = t0 + r0 + lane;                                                                         \
-      const bool act = lane < np && ex_tile_allows(tbits, t0, id);                                           \
-      const Key key = key_make(act ? m[lane * d] : zero, id);                                                \
-      wave_lds_sync(); /* m is rewritten by the next batch */                                                \
-      S.offer<I>(act && key_less(key, S.tau[I]) && !(A.self && id == qbase + (I)), key);                     \
-    }                                                                                                        \
-  }
-    ANN_EX_GEN_QUERY(0) ANN_EX_GEN_QUERY(1) ANN_EX_GEN_QUERY(2) ANN_EX_GEN_QUERY(3)
-#undef ANN_EX_GEN_QUERY
-  }
-  S.store(A.ws, qrel, A.qn, A.ranges, (int)blockIdx.y);
-}
-
-// exact_merge_kernel (reused) unpacks key_max() where a query has fewer than k allowed rows: those entries -> (n, +inf)
-__global__ void exact_tail_kernel(size_t count, size_t n, size_t *__restrict__ ids, FT *__restrict__ dists) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x)
-    if (ids[e] == (size_t)ANN_ID_NONE) ids[e] = n, dists[e] = ft_inf();
 }

@@ -1669,6 +1669,26 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
 static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size_t k, const TagQuery *tq, const u32 *codes,
                                    const unsigned char *pbits, int pb, size_t *ids, FT *dists, unsigned long long *scored,
                                    hipStream_t s);
+static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *radius, size_t *ids, FT *dists, u32 *counts,
+                               hipStream_t s);
+
+// How a fixed-mode call ends once stage 2 has written its rows of k: the appended rows merged into them ("stage2_network"
+// of annhip_stage_ms) -- the hashed ones through the buckets this call probes, the rest scanned exactly --, the trim of a
+// radius call (radius != NULL), the closing marks and the index's counters.  pbits: NULL where the call does not probe.
+static void fixed_mode_tail(annhip_index *ix, std::vector<hipEvent_t> *marks, hipStream_t s, size_t Q, const FT *y, int alias,
+                            size_t k, const TagQuery *tq, const u32 *codes, const unsigned char *pbits, size_t *ids_dev, FT *out_d,
+                            const FT *radius, u32 *counts_dev) {
+  unsigned long long *scored = ix->profile == 1 ? ix->d_rows + 8 : NULL;
+  if (ix->tail_mh) launch_tail_hash_merge(ix, Q, y, k, tq, codes, pbits, pbits ? ix->probe : 0, ids_dev, out_d, scored, s);
+  if (ix->tail_m > ix->tail_mh) launch_tail_merge(ix, Q, y, alias, k, tq, k, ids_dev, out_d, ids_dev, out_d, scored, s, ix->tail_mh);
+  // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
+  // so the trim is in neither the stage-1 nor the stage-2 figure)
+  if (radius) launch_radius_trim(Q, k, n_total(ix), radius, ids_dev, out_d, counts_dev, s);
+  seg_mark(ix, marks, s);
+  seg_mark(ix, marks, s);
+  if (marks) ix->seg_used.push_back(*marks);
+  ix->queries += (double)Q;
+}
 
 // ----------------------------------------------------------------------------- query
 // codes_ready: ws.codes already holds the hash codes of this batch (query_gpu computes them chunk by chunk while the
@@ -1736,18 +1756,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
                                      ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter, tq))
       die("fixed mode: stage-2 shape not supported");
     seg_mark(ix, marks, s);
-    // appended rows, merged into the rows just written ("stage2_network" of annhip_stage_ms): the hashed ones through the
-    // buckets this call probes, the rest scanned exactly
-    if (ix->tail_mh)
-      launch_tail_hash_merge(ix, Q, y, (size_t)k, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
-                             ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
-    if (ix->tail_m > ix->tail_mh)
-      launch_tail_merge(ix, Q, y, alias, (size_t)k, tq, (size_t)k, ids_dev, out_d, ids_dev, out_d,
-                        ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->tail_mh);
-    seg_mark(ix, marks, s);
-    seg_mark(ix, marks, s);
-    if (marks) ix->seg_used.push_back(marks_store);
-    ix->queries += (double)Q;
+    fixed_mode_tail(ix, marks, s, Q, y, alias, (size_t)k, tq, codes, pbits, ids_dev, out_d, NULL, NULL);
     return 0;
   }
   // pruned stage 1 (annhip_index_set_prune): preselect on the narrow copy, rescore on native rows -- the same answers
@@ -1984,9 +1993,10 @@ static void launch_stage2_kq(const QParams &P, size_t Q, const FT *y, int alias,
   HIPCHECK(hipGetLastError());
 }
 
-// query_impl's fixed branch with kq in the place of k (the caller has validated everything)
+// query_impl's fixed branch with kq in the place of k (the caller has validated everything).  radius != NULL
+// (annhip_query_radius, kq = its kcap): stage1_radius_kernel in stage 1, and the trim with counts_dev at the end.
 static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias, size_t kq,
-                         const TagQuery *tq, size_t *ids_dev, ftype *dists_dev) {
+                         const TagQuery *tq, const FT *radius, size_t *ids_dev, ftype *dists_dev, u32 *counts_dev) {
   if (!Q) return 0;
   if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
   const QParams P = query_params(ix);
@@ -2013,8 +2023,8 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
   u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
   u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-  if (ix->filter || tq || probing)
-    launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, NULL, cand_d, cand_i, nvt, nvo, s);
+  if (radius || ix->filter || tq || probing)
+    launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, radius, cand_d, cand_i, nvt, nvo, s);
   else launch_stage1(ix, P1, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
   seg_mark(ix, marks, s);
   hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kq, K1, P.L1, P.P1, cand_d,
@@ -2024,16 +2034,7 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
   launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
   seg_mark(ix, marks, s);
-  if (ix->tail_mh)
-    launch_tail_hash_merge(ix, Q, y, kq, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
-                           ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
-  if (ix->tail_m > ix->tail_mh)
-    launch_tail_merge(ix, Q, y, alias, kq, tq, kq, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s,
-                      ix->tail_mh);
-  seg_mark(ix, marks, s);
-  seg_mark(ix, marks, s);
-  if (marks) ix->seg_used.push_back(marks_store);
-  ix->queries += (double)Q;
+  fixed_mode_tail(ix, marks, s, Q, y, alias, kq, tq, codes, pbits, ids_dev, out_d, radius, counts_dev);
   return 0;
 }
 
@@ -2053,8 +2054,8 @@ extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip
     return -2;
   }
   const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
-  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, tagged ? &tq : NULL, ids_dev,
-                      dists_dev);
+  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, tagged ? &tq : NULL, NULL, ids_dev,
+                      dists_dev, NULL);
 }
 
 // ----------------------------------------------------------------------------- radius queries (annhip_query_radius)
@@ -2066,62 +2067,6 @@ static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *r
   if (blocks > 0x7FFFFFFFull) die("radius trim: batch too large");
   hipLaunchKernelGGL(radius_trim_kernel, dim3((unsigned)blocks), dim3(256), 0, s, Q, kcap, pad_id, radius, ids, dists, counts);
   HIPCHECK(hipGetLastError());
-}
-
-// query_k_impl with stage1_radius_kernel in stage 1 and the trim at the end (the caller has validated everything)
-static long query_radius_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
-                              size_t kcap, const FT *radius, const TagQuery *tq, size_t *ids_dev, ftype *dists_dev,
-                              u32 *counts_dev) {
-  if (!Q) return 0;
-  if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
-  const QParams P = query_params(ix);
-  QParams P1 = P;  // stage 1's view: k = kcap
-  P1.k = (int)kcap;
-  if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
-  const FT *y = reinterpret_cast<const FT *>(y_dev);
-  const int K1 = (int)kcap + 1;
-  std::vector<hipEvent_t> marks_store, *marks = ix->profile == 1 ? &marks_store : NULL;
-  seg_mark(ix, marks, s);
-  const bool probing = ix->probe > 0;
-  unsigned char *pbits = NULL;
-  u32 *codes = (u32 *)ws.codes.need(sizeof(u32) * Q * P.T);
-  if (probing) {
-    pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
-    launch_codes_probe(P, Q, y, codes, pbits, ix->probe, s, ws.d_fcount);
-  } else {
-    launch_codes(P, Q, y, codes, s, ws.d_fcount);
-  }
-  seg_mark(ix, marks, s);
-  u32 *top_i = (u32 *)ws.top_i.need(sizeof(u32) * Q * kcap);
-  FT *top_d = (FT *)ws.top_d.need(sizeof(FT) * Q * kcap);
-  FT *cand_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * K1);
-  u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
-  u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
-  u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-  launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, radius, cand_d, cand_i, nvt, nvo, s);
-  seg_mark(ix, marks, s);
-  hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kcap, K1, P.L1, P.P1,
-                     cand_d, cand_i, nvt, top_i, top_d, (int)kcap, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
-  HIPCHECK(hipGetLastError());
-  seg_mark(ix, marks, s);
-  FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kcap);
-  launch_stage2_kq(P, Q, y, alias, top_i, top_d, kcap, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL,
-                   s);
-  seg_mark(ix, marks, s);
-  if (ix->tail_mh)
-    launch_tail_hash_merge(ix, Q, y, kcap, tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d,
-                           ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
-  if (ix->tail_m > ix->tail_mh)
-    launch_tail_merge(ix, Q, y, alias, kcap, tq, kcap, ids_dev, out_d, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL,
-                      s, ix->tail_mh);
-  // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
-  // so the trim is in neither the stage-1 nor the stage-2 figure)
-  launch_radius_trim(Q, kcap, n_total(ix), radius, ids_dev, out_d, counts_dev, s);
-  seg_mark(ix, marks, s);
-  seg_mark(ix, marks, s);
-  if (marks) ix->seg_used.push_back(marks_store);
-  ix->queries += (double)Q;
-  return 0;
 }
 
 // A refusal launches nothing and leaves the outputs untouched; this entry never aborts on what it can refuse.
@@ -2141,8 +2086,8 @@ extern "C" long annhip_query_radius(annhip_index *ix, annhip_workspace *ws, void
     return -2;
   }
   const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
-  return query_radius_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kcap,
-                           reinterpret_cast<const FT *>(radius_dev), tagged ? &tq : NULL, ids_dev, dists_dev, counts_dev);
+  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kcap, tagged ? &tq : NULL,
+                      reinterpret_cast<const FT *>(radius_dev), ids_dev, dists_dev, counts_dev);
 }
 
 extern "C" int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev,
@@ -2652,13 +2597,13 @@ static int exact_check(size_t n, size_t d, size_t k, int self) {
 // LDS carve-up of one workgroup of the exact scan for a kernel that takes up to max_waves waves: the row tile, then per wave
 // the selection buffers (and the query + tree scratch of the any-d path), then the tile's validity words.  The one source
 // of this arithmetic: exact_run and launch_tail_merge (ann_tail_kernels.h) both size their launches with it.
-// filtered: 0 = every row, 1 = allow list (ann_filter_kernels.h), 2 = tag predicate, with or without an allow list
-// (ann_tag_kernels.h).  prefetch: the kernel moves the next tile through registers.  false: the row does not fit.
+// valid (ann_exact_kernels.h): every row, the allow list, or the tag predicate with or without an allow list.
+// prefetch: the kernel moves the next tile through registers.  false: the row does not fit.
 struct ExShape {
   size_t W, tile_rows, smem, cap;
   bool prefetch;
 };
-static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool prefetch, int filtered, ExShape &sh) {
+static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool prefetch, ExValid valid, ExShape &sh) {
   const size_t row_bytes = d * sizeof(FT);
   const size_t cap = k + ANN_EX_SLACK;
   size_t np = ANN_EX_GEN_ELEMS / d;
@@ -2668,26 +2613,29 @@ static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool pr
   auto tile_rows_of = [&](size_t W, bool pf) {
     return std::max<size_t>(1, (pf ? (size_t)ANN_EX_PF * 64 * W * 16 : (size_t)ANN_EX_GEN_TILE_BYTES) / row_bytes);
   };
-  auto smem_of = [&](size_t W, bool pf) {  // (filtered: the tile's words of the allow list behind the waves' buffers,
-    return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +  // tagged: its tag words before them)
-           (filtered == 2 ? sizeof(u32) * tile_rows_of(W, pf) : 0) +
-           (filtered ? sizeof(u32) * ANN_EX_TBITS(tile_rows_of(W, pf)) : 0);
+  auto smem_of = [&](size_t W, bool pf) {  // (EX_BITS: the tile's words of the allow list behind the waves' buffers,
+    return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +  // EX_TAGS: its tag words before them)
+           (valid == EX_TAGS ? sizeof(u32) * tile_rows_of(W, pf) : 0) +
+           (valid != EX_ALL ? sizeof(u32) * ANN_EX_TBITS(tile_rows_of(W, pf)) : 0);
   };
   size_t W = (size_t)max_waves;
   while (W > 1 && smem_of(W, prefetch) > ANN_EX_LDS_BUDGET) W--;
   if (prefetch && row_bytes > (size_t)ANN_EX_PF * 64 * W * 16) prefetch = false;  // one row is more than the threads hold
-  if (prefetch && filtered == 2 && tile_rows_of(W, true) > 64 * W) prefetch = false;  // ... or more tags: one per thread
+  if (prefetch && valid == EX_TAGS && tile_rows_of(W, true) > 64 * W) prefetch = false;  // ... or more tags: one per thread
   sh.W = W, sh.cap = cap, sh.prefetch = prefetch;
   sh.smem = smem_of(W, prefetch);
   sh.tile_rows = tile_rows_of(W, prefetch);
   return sh.smem <= 160 * 1024;
 }
-// Shape of one annhip_exact_knn call; launch(grid, block, smem, args) starts the scan of one chunk of queries.
-template <typename Launch>
+// Every instance of exact_scan_kernel / exact_scan_generic_kernel.  EX_BITS reads the allow list through the last argument,
+// EX_TAGS through G (ann_exact_kernels.h).
+typedef void (*ExScanKernel)(ExArgs, ExValidArgs, const u32 *);
+// Shape of one annhip_exact_knn call and its launches: the scan and the merge of every chunk of queries.
 static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, const FT *y, int self, size_t *ids_dev,
-                     FT *dists_dev, bool generic, int max_waves, bool prefetch, int filtered, Launch &&launch) {
+                     FT *dists_dev, bool generic, int max_waves, bool prefetch, ExValid valid, ExScanKernel kernel,
+                     const ExValidArgs &G) {
   ExShape sh;
-  if (!exact_shape(d, k, generic, max_waves, prefetch, filtered, sh)) return exact_refuse("row too long for the LDS of one CU");
+  if (!exact_shape(d, k, generic, max_waves, prefetch, valid, sh)) return exact_refuse("row too long for the LDS of one CU");
   const size_t W = sh.W, cap = sh.cap, smem = sh.smem, tile_rows = sh.tile_rows;
   prefetch = sh.prefetch;
   const size_t qpg = W * ANN_EX_QB;  // queries per workgroup
@@ -2718,13 +2666,15 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
   A.points = pts, A.y = y, A.ws = ws;
   A.n = (u32)n, A.range_rows = (u32)range_rows, A.d = (int)d, A.k = (int)k, A.self = self ? 1 : 0;
   A.tile_rows = (int)tile_rows, A.cap = (int)cap, A.ranges = (int)ranges, A.prefetch = prefetch ? 1 : 0;
+  allow_lds(kernel, smem);
   for (size_t q0 = 0; q0 < ycnt; q0 += qchunk) {
     const size_t qn = std::min(qchunk, ycnt - q0);
     A.q0 = (u32)q0, A.qn = (u32)qn;
-    launch(dim3((unsigned)((qn + qpg - 1) / qpg), (unsigned)ranges), dim3((unsigned)(64 * W)), smem, A);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((qn + qpg - 1) / qpg), (unsigned)ranges), dim3((unsigned)(64 * W)), smem, 0, A, G,
+                       G.bits);
     hipLaunchKernelGGL(exact_merge_kernel, dim3((unsigned)((qn + 3) / 4)), dim3(256), 0, 0, ws, (u32)qn, (int)ranges, (int)k,
                        ids_dev + q0 * k, dists_dev + q0 * k);
-    if (filtered)  // fewer than k allowed rows: the "no row" padding becomes (n, +inf)
+    if (valid != EX_ALL)  // fewer than k valid rows: the "no row" padding becomes (n, +inf)
       exact_tail_kernel<<<grid_for(qn * k, 256, 1024), 256>>>(qn * k, n, ids_dev + q0 * k, dists_dev + q0 * k);
     HIPCHECK(hipGetLastError());
   }
@@ -2733,34 +2683,46 @@ static int exact_run(size_t n, size_t d, size_t k, const FT *pts, size_t ycnt, c
   return 0;
 }
 
-extern "C" int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt,
-                                         const ftype *y_dev, int self, const uint32_t *bits_dev, size_t *ids_dev,
-                                         ftype *dists_dev) {
-  if (!bits_dev) return annhip_exact_knn(n, d, k, points_dev, ycnt, y_dev, self, ids_dev, dists_dev);
-  if (const int rc = exact_check(n, d, k, self)) return rc;
+// What the three entry points do once the call is valid: the kernel of the row layout and of the validity form, then
+// exact_run with that kernel's waves and prefetch.
+static int exact_scan(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev, int self,
+                      ExValid valid, const ExValidArgs &G, size_t *ids_dev, ftype *dists_dev) {
   if (!ycnt) return 0;
   gpu_init();
   const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
   FT *dd = reinterpret_cast<FT *>(dists_dev);
-  const u32 *bits = bits_dev;
   const int code = layout_code(d);
-  if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 1,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_generic_filtered_kernel, smem);
-                       hipLaunchKernelGGL(exact_scan_generic_filtered_kernel, grid, block, smem, 0, A, bits);
-                     });
+  if (layout_is_generic(code)) {
+    const ExScanKernel kernel = valid == EX_TAGS   ? exact_scan_generic_kernel<EX_TAGS>
+                                : valid == EX_BITS ? exact_scan_generic_kernel<EX_BITS>
+                                                   : exact_scan_generic_kernel<EX_ALL>;
+    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, valid, kernel, G);
+  }
   int rc = 1;
   with_value(QueryLayouts{}, code, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
-    if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 1,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_filtered_kernel<D>, smem);
-                       hipLaunchKernelGGL(exact_scan_filtered_kernel<D>, grid, block, smem, 0, A, bits);
-                     });
+    if constexpr (D != 0 && !OcCode<D>::GEN) {
+      const ExScanKernel kernel = valid == EX_TAGS   ? exact_scan_kernel<D, EX_TAGS>
+                                  : valid == EX_BITS ? exact_scan_kernel<D, EX_BITS>
+                                                     : exact_scan_kernel<D, EX_ALL>;
+      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, valid, kernel, G);
+    }
   });
   return rc;
+}
+
+extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                                int self, size_t *ids_dev, ftype *dists_dev) {
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, EX_ALL, ExValidArgs{}, ids_dev, dists_dev);
+}
+
+extern "C" int annhip_exact_knn_filtered(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt,
+                                         const ftype *y_dev, int self, const uint32_t *bits_dev, size_t *ids_dev,
+                                         ftype *dists_dev) {
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, bits_dev ? EX_BITS : EX_ALL, ExValidArgs{NULL, bits_dev, NULL, NULL},
+                    ids_dev, dists_dev);
 }
 
 extern "C" int annhip_exact_knn_tagged(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
@@ -2769,56 +2731,8 @@ extern "C" int annhip_exact_knn_tagged(size_t n, size_t d, size_t k, const ftype
                                        ftype *dists_dev) {
   if (!tags_dev || !qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
   if (const int rc = exact_check(n, d, k, self)) return rc;
-  if (!ycnt) return 0;
-  gpu_init();
-  const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
-  FT *dd = reinterpret_cast<FT *>(dists_dev);
-  const ExTagArgs G{tags_dev, bits_dev, qmask_dev, qvalue_dev};
-  const int code = layout_code(d);
-  if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 2,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_generic_tag_kernel, smem);
-                       hipLaunchKernelGGL(exact_scan_generic_tag_kernel, grid, block, smem, 0, A, G);
-                     });
-  int rc = 1;
-  with_value(QueryLayouts{}, code, [&](auto dc) {
-    constexpr int D = decltype(dc)::value;
-    if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 2,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_tag_kernel<D>, smem);
-                       hipLaunchKernelGGL(exact_scan_tag_kernel<D>, grid, block, smem, 0, A, G);
-                     });
-  });
-  return rc;
-}
-
-extern "C" int annhip_exact_knn(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
-                                int self, size_t *ids_dev, ftype *dists_dev) {
-  if (const int rc = exact_check(n, d, k, self)) return rc;
-  if (!ycnt) return 0;
-  gpu_init();
-  const FT *pts = reinterpret_cast<const FT *>(points_dev), *y = reinterpret_cast<const FT *>(y_dev);
-  FT *dd = reinterpret_cast<FT *>(dists_dev);
-  const int code = layout_code(d);
-  if (layout_is_generic(code))
-    return exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, true, ANN_EX_GEN_WAVES, false, 0,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_generic_kernel, smem);
-                       hipLaunchKernelGGL(exact_scan_generic_kernel, grid, block, smem, 0, A);
-                     });
-  int rc = 1;
-  with_value(QueryLayouts{}, code, [&](auto dc) {
-    constexpr int D = decltype(dc)::value;
-    if constexpr (D != 0 && !OcCode<D>::GEN)
-      rc = exact_run(n, d, k, pts, ycnt, y, self, ids_dev, dd, false, ExCfg<D>::WAVES, ExCfg<D>::PREFETCH, 0,
-                     [&](dim3 grid, dim3 block, size_t smem, const ExArgs &A) {
-                       allow_lds(exact_scan_kernel<D>, smem);
-                       hipLaunchKernelGGL(exact_scan_kernel<D>, grid, block, smem, 0, A);
-                     });
-  });
-  return rc;
+  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, EX_TAGS, ExValidArgs{tags_dev, bits_dev, qmask_dev, qvalue_dev},
+                    ids_dev, dists_dev);
 }
 
 extern "C" int annhip_exact_knn_host(size_t n, size_t d, size_t k, const ftype *points, size_t ycnt, const ftype *y,
@@ -2854,7 +2768,7 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
                               hipStream_t s, size_t skip) {
   if (!Q || ix->tail_m <= skip) return;
   const size_t d = ix->d;
-  const int filtered = tq ? 2 : ix->filter ? 1 : 0;
+  const ExValid valid = tq ? EX_TAGS : ix->filter ? EX_BITS : EX_ALL;
   TailArgs A;
   A.tail = ix->d_tail + skip * d, A.y = y, A.in_ids = in_ids, A.in_d = in_d, A.out_ids = ids, A.out_d = dists;
   A.bits = ix->filter, A.tags = tq ? tq->tags : NULL, A.qmask = tq ? tq->qmask : NULL, A.qvalue = tq ? tq->qvalue : NULL;
@@ -2863,7 +2777,7 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
   A.d = (int)d, A.k = (int)k, A.kin = (int)kin, A.self = alias ? 1 : 0;
   auto shape = [&](bool generic, int max_waves, bool prefetch) {
     ExShape sh;
-    if (!exact_shape(d, k, generic, max_waves, prefetch, filtered, sh)) die("launch_tail_merge: row too long for the LDS of one CU");
+    if (!exact_shape(d, k, generic, max_waves, prefetch, valid, sh)) die("launch_tail_merge: row too long for the LDS of one CU");
     A.tile_rows = (int)sh.tile_rows, A.cap = (int)sh.cap, A.prefetch = sh.prefetch ? 1 : 0;
     return sh;
   };
@@ -2883,9 +2797,9 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
           allow_lds(kernel, sh.smem);
           hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, A);
         };
-        if (filtered == 2) go(tail_merge_kernel<D, TAIL_TAGS>);
-        else if (filtered == 1) go(tail_merge_kernel<D, TAIL_BITS>);
-        else go(tail_merge_kernel<D, TAIL_ALL>);
+        if (valid == EX_TAGS) go(tail_merge_kernel<D, EX_TAGS>);
+        else if (valid == EX_BITS) go(tail_merge_kernel<D, EX_BITS>);
+        else go(tail_merge_kernel<D, EX_ALL>);
       }
     });
   }
@@ -2900,7 +2814,7 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
                                    hipStream_t s) {
   if (!Q || !ix->tail_mh) return;
   const size_t d = ix->d;
-  const int filtered = tq ? 2 : ix->filter ? 1 : 0;
+  const ExValid valid = tq ? EX_TAGS : ix->filter ? EX_BITS : EX_ALL;
   TailHashArgs A;
   A.t.tail = ix->d_tail, A.t.y = y, A.t.in_ids = ids, A.t.in_d = dists, A.t.out_ids = ids, A.t.out_d = dists;
   A.t.bits = ix->filter, A.t.tags = tq ? tq->tags : NULL, A.t.qmask = tq ? tq->qmask : NULL, A.t.qvalue = tq ? tq->qvalue : NULL;
@@ -2914,7 +2828,7 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
   };
   auto shape = [&](bool generic, int max_waves) {
     ExShape sh;
-    if (!exact_shape(d, k, generic, max_waves, false, filtered, sh)) die("launch_tail_hash_merge: row too long for the LDS of one CU");
+    if (!exact_shape(d, k, generic, max_waves, false, valid, sh)) die("launch_tail_hash_merge: row too long for the LDS of one CU");
     A.t.cap = (int)sh.cap;
     size_t np = ANN_EX_GEN_ELEMS / d;
     np = np < 1 ? 1 : (np > ANN_WAVE ? ANN_WAVE : np);
@@ -2942,9 +2856,9 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
           allow_lds(kernel, sh.smem);
           hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, A);
         };
-        if (filtered == 2) go(tail_hash_merge_kernel<D, TAIL_TAGS>);
-        else if (filtered == 1) go(tail_hash_merge_kernel<D, TAIL_BITS>);
-        else go(tail_hash_merge_kernel<D, TAIL_ALL>);
+        if (valid == EX_TAGS) go(tail_hash_merge_kernel<D, EX_TAGS>);
+        else if (valid == EX_BITS) go(tail_hash_merge_kernel<D, EX_BITS>);
+        else go(tail_hash_merge_kernel<D, EX_ALL>);
       }
     });
   }
@@ -3075,7 +2989,7 @@ static int launch_rerank(const char *who, size_t n, size_t m, size_t d, const FT
   };
   auto shape = [&](int max_waves) {
     ExShape sh;
-    (void)exact_shape(d, k, generic, max_waves, false, 0, sh);  // for cap: no row tile here, the fit is tested below
+    (void)exact_shape(d, k, generic, max_waves, false, EX_ALL, sh);  // for cap: no row tile here, the fit is tested below
     size_t np = ANN_EX_GEN_ELEMS / d;
     np = np < 1 ? 1 : (np > ANN_WAVE ? ANN_WAVE : np);
     const size_t wave_bytes = sizeof(Key) * (sh.cap + k) + (generic ? (((1 + np) * d * sizeof(FT) + 15) & ~(size_t)15) : 0) +

@@ -117,10 +117,10 @@ __device__ __forceinline__ int thash_reject(const TailHashArgs &A, const ThashWa
     const u32 j = L.cj[ok ? e : e0], t = L.ct[ok ? e : e0];
     const u32 *cj = A.tcodes + (size_t)j * A.T;
     for (u32 t2 = 0; ok && t2 < t; t2++) ok = !thash_hits(L.qc[t2] ^ cj[t2], L.pm[t2]);
-    if constexpr (V != TAIL_ALL) {
+    if constexpr (V != EX_ALL) {
       const u32 id = A.t.n + j;
       if (ok && bits) ok = (bits[id >> 5] >> (id & 31)) & 1u;
-      if (V == TAIL_TAGS && ok) ok = (tags[id] & qm) == qv;
+      if (V == EX_TAGS && ok) ok = (tags[id] & qm) == qv;
     }
     const u64 mm = __ballot(ok);
     wave_lds_sync();  // the pass has read its entries; ns + rank <= e
@@ -202,8 +202,8 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_hash_merge_kernel(T
     else a[c] = oc_load_chunk<D, false>(yq, ln.p + c * ln.oc, d);
   }
   u32 qm = 0, qv = 0;
-  if constexpr (V == TAIL_TAGS) qm = A.t.qmask[q], qv = A.t.qvalue[q];
-  const u32 *__restrict__ bits = V == TAIL_ALL ? (const u32 *)NULL : A.t.bits;
+  if constexpr (V == EX_TAGS) qm = A.t.qmask[q], qv = A.t.qvalue[q];
+  const u32 *__restrict__ bits = V == EX_ALL ? (const u32 *)NULL : A.t.bits;
   thash_load_query(A, L, q);
   tail_seed<0>(S, A.t, q, true);
   u32 nsc = 0;
@@ -308,8 +308,8 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_hash_merge_generic
     }
     wave_lds_sync();  // the chunk is refilled
   };
-  if (tags) thash_enumerate<TAIL_TAGS>(A, L, q, bits, tags, qm, qv, score);
-  else thash_enumerate<TAIL_BITS>(A, L, q, bits, tags, qm, qv, score);
+  if (tags) thash_enumerate<EX_TAGS>(A, L, q, bits, tags, qm, qv, score);
+  else thash_enumerate<EX_BITS>(A, L, q, bits, tags, qm, qv, score);
   tail_store<0>(S, A.t, q, true);
   if (A.t.scored && lane == 0 && nsc) atomicAdd(&A.t.scored[(blockIdx.x & 63u) * 8u], (unsigned long long)nsc);
 }

@@ -10,18 +10,16 @@
 // The distances come out of the same trees as in exact_scan_kernel (ex_reduce: row_reduce / ex_reduce_pk / row_reduce_oc,
 // and the literal in-place tree of the any-d form), so they are the query path's bits.  Tail row j has id n + j.
 //
-// Validity (TailValid) is what the filtered and tagged exact kernels test, on ids n + j: the allow-list words and the tag
+// Validity (ExValid) is what exact_scan_kernel's EX_BITS and EX_TAGS forms test, on ids n + j: the allow-list words and the tag
 // words of a tile are staged in LDS behind the waves' buffers and tested before a row is scored.  The bitmap and the tag
 // array cover [0, n_total): the index extends its copies on append (ann_host.hip).
 //
 // The input row may be the output row (the query path merges in place): a wave reads the rows of its own queries before
 // it writes them, and no other wave touches them.  in_ids / in_d hold kin <= k entries per query (kin < k only where the
 // built rows cannot fill a row: the exact entries on an index with n - alias < k).
-// LDS carve-up: exact_shape() on the host, the one that sizes exact_scan_kernel and its filtered and tagged forms.
+// LDS carve-up: exact_shape() on the host, the one that sizes every form of exact_scan_kernel.
 #pragma once
 #include "ann_tag_kernels.h"
-
-enum TailValid { TAIL_ALL = 0, TAIL_BITS = 1, TAIL_TAGS = 2 };  // TAIL_TAGS: the tag test, and the allow list where bits != NULL
 
 struct TailArgs {
   const FT *tail, *y;      // tail rows [m][d]; queries [Q][d]
@@ -75,9 +73,9 @@ __device__ __forceinline__ void tail_store(ExSel &S, const TailArgs &A, u32 q, b
 template <int V>
 __device__ __forceinline__ void tail_fill_words(const TailArgs &A, u32 *ttags, u32 *tbits, u32 t0, u32 rows) {
   const u32 id0 = A.n + t0;
-  if constexpr (V == TAIL_TAGS)
+  if constexpr (V == EX_TAGS)
     for (u32 i = threadIdx.x; i < rows; i += blockDim.x) ttags[i] = A.tags[id0 + i];
-  if constexpr (V != TAIL_ALL)
+  if constexpr (V != EX_ALL)
     if (A.bits)
       for (u32 i = threadIdx.x; i < ex_tile_words(id0, rows); i += blockDim.x) tbits[i] = A.bits[(id0 >> 5) + i];
 }
@@ -92,8 +90,8 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
   const size_t tile_bytes = ((size_t)A.tile_rows * d * sizeof(FT) + 15) & ~(size_t)15;
   Key *kbase = reinterpret_cast<Key *>(smem + tile_bytes) + (size_t)w * ((size_t)ANN_EX_QB * A.cap + A.k);
   u32 *ttags = reinterpret_cast<u32 *>(smem + tile_bytes + (size_t)W * sizeof(Key) * ((size_t)ANN_EX_QB * A.cap + A.k));
-  u32 *tbits = V == TAIL_TAGS ? ttags + A.tile_rows : ttags;
-  const u32 *__restrict__ bits = V == TAIL_ALL ? (const u32 *)NULL : A.bits;
+  u32 *tbits = V == EX_TAGS ? ttags + A.tile_rows : ttags;
+  const u32 *__restrict__ bits = V == EX_ALL ? (const u32 *)NULL : A.bits;
   // first query of this wave; the wave index is uniform, which the compiler cannot see: a scalar register, and so are the
   // four ids of the aliased test and the four "query inside the batch" flags
   const u32 qbase = __builtin_amdgcn_readfirstlane((blockIdx.x * W + w) * ANN_EX_QB), qend = A.Q;
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
   for (int i = 0; i < ANN_EX_QB; i++) {
     const u32 q = qbase + i < qend ? qbase + i : qend - 1;  // loads stay inside y; the result is never admitted
     const FT *yq = A.y + (size_t)q * d;
-    if constexpr (V == TAIL_TAGS) {
+    if constexpr (V == EX_TAGS) {
       const u32 qu = __builtin_amdgcn_readfirstlane(q);
       qm[i] = A.qmask[qu], qv[i] = A.qvalue[qu];
     } else {
@@ -139,24 +137,24 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
     // the next tile's loads are in flight while this one is scored
     typedef FT pf_t __attribute__((ext_vector_type(ANN_VEC)));
     pf_t pf0 = 0, pf1 = 0;
-    u32 pfw = 0;  // TAIL_BITS: the next tile's bitmap word of this thread; TAIL_TAGS: its tag word (exact_scan_tag_kernel)
+    u32 pfw = 0;  // EX_BITS: the next tile's bitmap word of this thread; EX_TAGS: its tag word (exact_scan_kernel)
     if constexpr (ExCfg<D>::PREFETCH) {
       if (prefetch && rows1) {  // unconditional loads from clamped addresses: plain registers, nothing waits here
         const pf_t *src = reinterpret_cast<const pf_t *>(A.tail + (size_t)t1 * d);
         const u32 last = rows1 * (u32)(d / ANN_VEC) - 1;
         pf0 = src[min(threadIdx.x, last)];
         pf1 = src[min(threadIdx.x + blockDim.x, last)];
-        if constexpr (V == TAIL_BITS) pfw = bits[((A.n + t1) >> 5) + min(threadIdx.x, ex_tile_words(A.n + t1, rows1) - 1)];
-        if constexpr (V == TAIL_TAGS) pfw = A.tags[A.n + t1 + min(threadIdx.x, rows1 - 1)];
+        if constexpr (V == EX_BITS) pfw = bits[((A.n + t1) >> 5) + min(threadIdx.x, ex_tile_words(A.n + t1, rows1) - 1)];
+        if constexpr (V == EX_TAGS) pfw = A.tags[A.n + t1 + min(threadIdx.x, rows1 - 1)];
       }
     }
     for (u32 r0 = 0; r0 < rows; r0 += ln.rpw) {
       const u32 r = r0 + ln.g;
       const bool act = ln.valid && r < rows;
       bool allowed = act;
-      if constexpr (V != TAIL_ALL) {
+      if constexpr (V != EX_ALL) {
         allowed = act && (!bits || ex_tile_allows(tbits, id0, id0 + r));
-        if constexpr (V == TAIL_TAGS) {
+        if constexpr (V == EX_TAGS) {
           const u32 tg = ttags[act ? r : r0];
           allowed = allowed && ((tg & qm[0]) == qv[0] || (tg & qm[1]) == qv[1] || (tg & qm[2]) == qv[2] || (tg & qm[3]) == qv[3]);
         }
@@ -177,13 +175,13 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
 #pragma unroll
       for (int i = 0; i < ANN_EX_QB; i++) key[i] = key_make(ex_reduce<D>(a[i], b, ln.oc, ln.p, d), id);
       u32 tg = 0;
-      if constexpr (V == TAIL_TAGS) {
+      if constexpr (V == EX_TAGS) {
         asm volatile("" ::: "memory");  // a second LDS read, not a register kept through the reduction
         tg = ttags[act ? r : r0];
       }
 #pragma unroll
       for (int i = 0; i < ANN_EX_QB; i++) {
-        ok[i] = head && (V != TAIL_TAGS || (tg & qm[i]) == qv[i]) && !(A.self && id == qbase + i);
+        ok[i] = head && (V != EX_TAGS || (tg & qm[i]) == qv[i]) && !(A.self && id == qbase + i);
         pass[i] = ok[i] && key_less(key[i], S.tau[i]);
       }
       if (A.scored) {  // wave-uniform; a query beyond the batch counts nothing
@@ -207,10 +205,10 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
         const u32 pieces = rows1 * (u32)(d / ANN_VEC);
         if (threadIdx.x < pieces) t[threadIdx.x] = pf0;
         if (threadIdx.x + blockDim.x < pieces) t[threadIdx.x + blockDim.x] = pf1;
-        if constexpr (V == TAIL_BITS) {
+        if constexpr (V == EX_BITS) {
           if (threadIdx.x < ex_tile_words(A.n + t1, rows1)) tbits[threadIdx.x] = pfw;
         }
-        if constexpr (V == TAIL_TAGS) {
+        if constexpr (V == EX_TAGS) {
           if (threadIdx.x < rows1) ttags[threadIdx.x] = pfw;  // (rows1 <= blockDim.x: exact_shape)
           if (bits && threadIdx.x < ex_tile_words(A.n + t1, rows1)) tbits[threadIdx.x] = bits[((A.n + t1) >> 5) + threadIdx.x];
         }
@@ -277,33 +275,7 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_merge_generic_kern
       const u32 qu = __builtin_amdgcn_readfirstlane(qbase + (I));                                            \
       qm = A.qmask[qu], qv = A.qvalue[qu];                                                                   \
     }                                                                                                        \
-    wave_lds_sync();                                                                                         \
-    for (int z = lane; z < d; z += ANN_WAVE) yq[z] = A.y[(size_t)(qbase + (I)) * d + z];                     \
-    wave_lds_sync();                                                                                         \
-    for (u32 r0 = 0; r0 < rows; r0 += NP) {                                                                  \
-      const int np = (int)min((u32)NP, rows - r0);                                                           \
-      for (int it = lane; it < (np << sh0); it += ANN_WAVE) {                                                \
-        const int pr = it >> sh0, z = it & ((1 << sh0) - 1);                                                 \
-        if (z < d) {                                                                                         \
-          const FT df = yq[z] - tile[(size_t)(r0 + pr) * d + z];                                             \
-          m[pr * d + z] = df * df;                                                                           \
-        }                                                                                                    \
-      }                                                                                                      \
-      wave_lds_sync();                                                                                       \
-      int sh = sh0;                                                                                          \
-      for (int s = d; s >> 1; s >>= 1) {                                                                     \
-        const int h = s >> 1;                                                                                \
-        while (sh > 0 && (1 << (sh - 1)) >= h) sh--; /* h <= 1 << sh */                                      \
-        for (int it = lane; it < (np << sh); it += ANN_WAVE) {                                               \
-          const int pr = it >> sh, z = it & ((1 << sh) - 1);                                                 \
-          if (z < h) {                                                                                       \
-            FT *mp = m + pr * d;                                                                             \
-            const FT g = ((s & 1) && z == 0) ? mp[s - 1] : zero;                                             \
-            mp[z] = mp[z] + (mp[z + h] + g);                                                                 \
-          }                                                                                                  \
-        }                                                                                                    \
-        wave_lds_sync();                                                                                     \
-      }                                                                                                      \
+    ANN_EX_GEN_QUERY(qbase + (I), {                                                                          \
       const u32 id = id0 + r0 + lane;                                                                        \
       const bool act = lane < np && (!tags || (ttags[r0 + lane] & qm) == qv) &&                              \
                        (!bits || ex_tile_allows(tbits, id0, id)) && !(A.self && id == qbase + (I));          \
@@ -311,7 +283,7 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_merge_generic_kern
       wave_lds_sync(); /* m is rewritten by the next batch */                                                \
       if (A.scored) nsc += (u32)__builtin_popcountll(__ballot(act));                                         \
       S.offer<I>(act && key_less(key, S.tau[I]), key);                                                       \
-    }                                                                                                        \
+    })                                                                                                       \
   }
     ANN_TAIL_GEN_QUERY(0) ANN_TAIL_GEN_QUERY(1) ANN_TAIL_GEN_QUERY(2) ANN_TAIL_GEN_QUERY(3)
 #undef ANN_TAIL_GEN_QUERY

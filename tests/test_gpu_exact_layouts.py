@@ -1,5 +1,5 @@
-"""GPU: the filtered and tagged exact scans (annhip_exact_knn_filtered, annhip_exact_knn_tagged; exact_scan_filtered_kernel,
-exact_scan_tag_kernel and their generic forms) at a row length of every layout code, as tests/test_gpu_exact_knn.py::
+"""GPU: the filtered and tagged exact scans (annhip_exact_knn_filtered, annhip_exact_knn_tagged; the EX_BITS and EX_TAGS
+instances of exact_scan_kernel and exact_scan_generic_kernel) at a row length of every layout code, as tests/test_gpu_exact_knn.py::
 test_every_layout does for the unfiltered scan.  The other bit-exact oracles of the suite (tests/test_gpu_query_k.py,
 tests/test_gpu_tail.py) use these scans as their ground truth at whatever row length they run.
 

@@ -1,8 +1,14 @@
-"""python tools/devcode_diff.py OLD.so NEW.so -- the gfx950 device code of two builds of a backend library, kernel by
-kernel: the proof that a host-side change (how the launchers pick kernels) left every kernel as it was.  Prints the
-kernels only one side has and every function of both whose disassembly or `llvm-readelf --notes` metadata differs
-(comments, the PC-relative s_add_u32 immediate after an s_getpc_b64 and trailing padding ignored: the .text layout
-may move).  Exit status 1 if a function differs or NEW has a kernel OLD has not."""
+r"""python tools/devcode_diff.py OLD.so NEW.so [--map 'REGEX=>REPLACEMENT' ...] -- the gfx950 device code of two builds
+of a backend library, kernel by kernel: the proof that a host-side change (how the launchers pick kernels) left every
+kernel as it was.  Prints the kernels only one side has and every function of both whose disassembly or
+`llvm-readelf --notes` metadata differs (comments, the PC-relative s_add_u32 immediate after an s_getpc_b64 and trailing
+padding ignored: the .text layout may move).  Exit status 1 if a function differs or NEW has a kernel OLD has not.
+
+--map renames OLD's functions before the comparison (re.sub on the demangled name, e.g.
+'exact_scan_kernel<(-?\d+)>\(ExArgs\)=>exact_scan_kernel<\1, 0>(ExArgs, ExValidArgs, unsigned int const*)'), so that a kernel is compared
+with its successor.  A renamed kernel's argument list may have changed shape: for such a pair the immediate offsets of
+scalar loads (where the kernel arguments are read) and the metadata lines that carry the name, the arguments and
+`.kernarg_segment_size` are left out of the comparison; everything else counts."""
 import os
 import re
 import subprocess
@@ -47,21 +53,52 @@ def describe(so, tmp):
                 meta[names[0]] = "\n".join(cur)
             cur = []
         cur.append(line)
-    return kernels, code, meta
+    # mangled -> demangled, from the symbol table read twice
+    pretty = {a.split()[7]: b.split(None, 7)[7] for a, b in zip(run("llvm-readelf", "-s", "-W", co).splitlines(),
+                                                                run("llvm-readelf", "-s", "-W", "--demangle", co).splitlines())
+              if len(a.split()) == 8}
+    pretty = {f: pretty.get(f, f) for f in kernels | set(code) | set(meta)}
+    return ({pretty[k] for k in kernels}, {pretty[f]: c for f, c in code.items()}, {pretty[k]: m for k, m in meta.items()})
 
 
-def main(old, new):
+def loose(ins, meta):
+    """a renamed kernel without what follows its argument list"""
+    ins = [re.sub(r"^(s_load_\S+ .*) \S+$", r"\1 <offset>", i) for i in ins]
+    keep, skip = [], False
+    for line in (meta or "").splitlines():
+        if line.startswith("    .args:"):
+            skip = True
+        elif skip and re.match(r"^    \.", line):
+            skip = False
+        if not skip and not re.match(r"^    \.(name|symbol|kernarg_segment_size):", line):
+            keep.append(line)
+    return ins, keep
+
+
+def main(old, new, maps=()):
     with tempfile.TemporaryDirectory() as tmp:
         (ko, co, mo), (kn, cn, mn) = describe(old, tmp), describe(new, tmp)
+    renamed = set()
+    for rule in maps:
+        pat, repl = rule.split("=>", 1)
+        to = {f: re.sub(pat, repl, f) for f in set(ko) | set(co) | set(mo)}
+        renamed |= {t for f, t in to.items() if t != f}
+        ko = {to[f] for f in ko}
+        co, mo = {to[f]: c for f, c in co.items()}, {to[f]: m for f, m in mo.items()}
+    for f in renamed & set(co) & set(cn):
+        (co[f], mo[f]), (cn[f], mn[f]) = loose(co[f], mo.get(f)), loose(cn[f], mn.get(f))
     print("kernels: %d -> %d; only in OLD: %d; only in NEW: %d" % (len(ko), len(kn), len(ko - kn), len(kn - ko)))
     for k in sorted(kn - ko):
         print("  added:", k)
     bad = [f for f in sorted(set(co) & set(cn)) if co[f] != cn[f] or mo.get(f) != mn.get(f)]
     for f in bad:
         print("  differs:", f, "(code)" if co[f] != cn[f] else "(metadata)")
-    print("functions compared: %d, differing: %d" % (len(set(co) & set(cn)), len(bad)))
+    print("functions compared: %d (renamed: %d), differing: %d" % (len(set(co) & set(cn)), len(renamed & set(co) & set(cn)), len(bad)))
     return 1 if bad or kn - ko else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    argv = sys.argv[1:]
+    maps = [argv[i + 1] for i, a in enumerate(argv) if a == "--map"]
+    files = [a for i, a in enumerate(argv) if a != "--map" and (i == 0 or argv[i - 1] != "--map")]
+    sys.exit(main(files[0], files[1], maps))

@@ -4,8 +4,8 @@ The product is the C-ABI shared library under csrc/ (include/*.h); this package 
 mirror of the reference's interface used by the tests, the bench and multi-GPU hosts.
 """
 from . import _lib
-from .api import (HostStream, Index, Save, checksum, exact_knn, gpu_cleanup, gpu_init, precomp, query, radius_recall, radius_trim,
+from .api import (HostStream, Index, Save, checksum, exact_knn, gpu_cleanup, gpu_init, order_key, precomp, query, radius_recall, radius_trim,
                   recall_at_k, recall_ranks, recall_summary, rerank, synth_randnorm)
 
-__all__ = ["HostStream", "Index", "Save", "precomp", "query", "recall_ranks", "recall_summary", "exact_knn", "recall_at_k", "radius_trim", "radius_recall", "rerank", "gpu_init", "gpu_cleanup", "synth_randnorm", "checksum",
+__all__ = ["HostStream", "Index", "Save", "precomp", "query", "recall_ranks", "recall_summary", "exact_knn", "recall_at_k", "radius_trim", "radius_recall", "rerank", "gpu_init", "gpu_cleanup", "synth_randnorm", "checksum", "order_key",
            "_lib"]

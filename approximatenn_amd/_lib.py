@@ -115,6 +115,12 @@ def load(prec="f32"):
     lib.annhip_query_radius.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, vp, vp]
     lib.annhip_index_exact_query_radius.restype = C.c_int
     lib.annhip_index_exact_query_radius.argtypes = [vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, vp, vp]
+    lib.annhip_query_between.restype = C.c_long
+    lib.annhip_query_between.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.annhip_index_exact_query_between.restype = C.c_int
+    lib.annhip_index_exact_query_between.argtypes = [vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.annhip_exact_knn_between.restype = C.c_int
+    lib.annhip_exact_knn_between.argtypes = [sz, sz, sz, vp, sz, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.annhip_radius_trim.restype = C.c_int
     lib.annhip_radius_trim.argtypes = [sz, sz, sz, vp, vp, vp, vp, vp]
     lib.annhip_rerank.restype = C.c_int
@@ -242,6 +248,7 @@ EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp
             "annhip_index_exact_query_tagged",
             "annhip_query_k", "annhip_index_max_query_k", "annhip_index_exact_query_k",
             "annhip_query_radius", "annhip_index_exact_query_radius", "annhip_radius_trim",
+            "annhip_query_between", "annhip_index_exact_query_between", "annhip_exact_knn_between",
             "annhip_rerank", "annhip_index_rerank",
             "annhip_index_append", "annhip_index_reserve_tail", "annhip_index_tail", "annhip_index_copy_rows", "annhip_index_drop_tail",
             "annhip_index_hash_tail", "annhip_index_tail_hashed",

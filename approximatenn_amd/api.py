@@ -266,10 +266,31 @@ def _words_dev(words, length, device, what):
 
 def _where_dev(where, Q, device):
     """where = (qmask, qvalue), each as _words_dev takes it -> two int32 device tensors [Q]: query q's predicate is
-    (tags[i] & qmask[q]) == qvalue[q]."""
-    if not isinstance(where, (tuple, list)) or len(where) != 2:
-        raise ValueError("where must be a pair (qmask, qvalue)")
-    return _words_dev(where[0], Q, device, "where[0] (qmask)"), _words_dev(where[1], Q, device, "where[1] (qvalue)")
+    (tags[i] & qmask[q]) == qvalue[q].  where = (qmask, qlo, qhi) -> three: qlo[q] <= (tags[i] & qmask[q]) <= qhi[q],
+    unsigned (the *_between calls)."""
+    if not isinstance(where, (tuple, list)) or len(where) not in (2, 3):
+        raise ValueError("where must be a pair (qmask, qvalue) or a triple (qmask, qlo, qhi)")
+    if len(where) == 2:  # (the pair's path as it always was: it sits inside the timed step of every tagged call)
+        return _words_dev(where[0], Q, device, "where[0] (qmask)"), _words_dev(where[1], Q, device, "where[1] (qvalue)")
+    return (_words_dev(where[0], Q, device, "where[0] (qmask)"), _words_dev(where[1], Q, device, "where[1] (qlo)"),
+            _words_dev(where[2], Q, device, "where[2] (qhi)"))
+
+
+def order_key(values):
+    """The order-preserving map of a numeric column into tag words -> numpy uint32 of the same shape: a <= b iff
+    order_key(a) <= order_key(b) as unsigned words, so the result serves as, or inside, a tag word and as the bounds of
+    where=(qmask, qlo, qhi).  int32: x ^ 0x80000000.  float32: the bits with the sign bit flipped for non-negative values
+    and all bits flipped for negative ones; -0.0 counts as +0.0.  ValueError for NaN and for any other dtype.  A float
+    window [a, b] is where=(0xFFFFFFFF, order_key(a), order_key(b))."""
+    v = np.asarray(values)
+    if v.dtype == np.int32:
+        return v.view(np.uint32) ^ np.uint32(0x80000000)
+    if v.dtype == np.float32:
+        if np.isnan(v).any():
+            raise ValueError("order_key: NaN has no place in the order")
+        b = (v + np.float32(0)).view(np.uint32)  # -0.0 + 0.0 = +0.0
+        return np.where(b >> np.uint32(31), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    raise ValueError("order_key: values must be int32 or float32, got %s" % v.dtype)
 
 
 def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, allow=None, tags=None, where=None):
@@ -282,7 +303,8 @@ def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, al
     tags + where: annhip_exact_knn_tagged -- tags: the rows' 32-bit tag words (numpy uint32 [n] or int32 device tensor [n]),
     where = (qmask, qvalue) (numpy uint32 [Q] or int32 device tensors [Q]): row i competes for query q iff
     (tags[i] & qmask[q]) == qvalue[q]; allow may be given too and is ANDed with that test.  One of the two without the
-    other is a ValueError."""
+    other is a ValueError.  where = (qmask, qlo, qhi): annhip_exact_knn_between -- qlo[q] <= (tags[i] & qmask[q]) <= qhi[q],
+    unsigned compares."""
     import torch
     if (tags is None) != (where is None):
         raise ValueError("exact_knn: tags and where=(qmask, qvalue) go together")
@@ -301,9 +323,18 @@ def exact_knn(points, y, k, self_exclude=False, out_ids=None, out_dists=None, al
     assert ids.is_contiguous() and dists.is_contiguous() and ids.dtype == torch.int64 and dists.dtype == y.dtype
     if tags is not None:
         tg = _words_dev(tags, points.shape[0], y.device, "tags")
-        qm, qv = _where_dev(where, Q, y.device)
+        pred = _where_dev(where, Q, y.device)
         bits = _pack_allow_dev(lib, allow, points.shape[0]) if allow is not None else None
         torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+        if len(pred) == 3:
+            rc = lib.annhip_exact_knn_between(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(),
+                                              int(bool(self_exclude)), tg.data_ptr(), bits.data_ptr() if bits is not None else None,
+                                              pred[0].data_ptr(), pred[1].data_ptr(), pred[2].data_ptr(), ids.data_ptr(),
+                                              dists.data_ptr())
+            if rc != 0:
+                raise ValueError("annhip_exact_knn_between refused n=%d k=%d self_exclude=%r" % (points.shape[0], k, bool(self_exclude)))
+            return ids, dists
+        qm, qv = pred
         rc = lib.annhip_exact_knn_tagged(points.shape[0], points.shape[1], k, points.data_ptr(), Q, y.data_ptr(),
                                          int(bool(self_exclude)), tg.data_ptr(), bits.data_ptr() if bits is not None else None,
                                          qm.data_ptr(), qv.data_ptr(), ids.data_ptr(), dists.data_ptr())
@@ -803,10 +834,22 @@ class Index:
         k: None = the index's k, the calls above, unchanged.  An integer: annhip_query_k -- fixed mode with the k of this
         call, 1 <= k <= max_query_k, -> (ids int64 [Q,k], sq dists [Q,k], 0); with or without where=, on `stream` / `ws`
         as where= is.  ValueError for a bool or a non-integer and where the library refuses (fixed mode off, k out of
-        range, where= without tags, a resharded index); nothing is launched then and the outputs are untouched."""
+        range, where= without tags, a resharded index); nothing is launched then and the outputs are untouched.
+        where = (qmask, qlo, qhi), each as above: annhip_query_between -- row i competes for query q iff
+        qlo[q] <= (tags[i] & qmask[q]) <= qhi[q], unsigned; with or without k=, -> (ids, dists, rc); refusals as above."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if isinstance(where, (tuple, list)) and len(where) == 3:
+            kq = self.k if k is None else self._check_k(k)
+            if kq < 1:
+                raise ValueError("query(k=...): k must be at least 1")
+            pred = _where_dev(where, Q, y.device)
+            ids = out_ids if out_ids is not None else torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+            dists = out_dists if out_dists is not None else torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+            assert tuple(ids.shape) == (Q, kq) and tuple(dists.shape) == (Q, kq) and ids.is_contiguous() and dists.is_contiguous()
+            rc = self._between(y, alias, kq, None, pred, ids, dists, None, ws, stream)
+            return ids, dists, rc
         if k is not None:
             k = self._check_k(k)
             if k < 1:
@@ -852,6 +895,43 @@ class Index:
                                            int(alias), mode, ids.data_ptr(), dists.data_ptr())
         return ids, dists, nex
 
+    def _between(self, y, alias, kq, rad, pred, ids, dists, counts, ws, stream):
+        """annhip_query_between on `stream` / `ws`: the stream and lifetime handling of the pair form's arrays."""
+        import torch
+        if stream is not None and torch.cuda.current_stream(y.device) != stream:
+            stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate (and radius) arrays were made on that one
+        # (a radius call may have no rows: annhip_query_radius wants non-NULL pointers then, as Index.query_radius gives it)
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device) if rad is not None else None
+        rc = self.lib.annhip_query_between(self.h, ws, stream.cuda_stream if stream is not None else None, y.shape[0], y.data_ptr(),
+                                           int(alias), kq, _ptr(rad, hold) if rad is not None else None, pred[0].data_ptr(),
+                                           pred[1].data_ptr(), pred[2].data_ptr(),
+                                           _ptr(ids, hold) if rad is not None else ids.data_ptr(), dists.data_ptr(),
+                                           counts.data_ptr() if counts is not None else None)
+        if rc == -2:
+            raise ValueError("annhip_query_between refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
+                             % (kq, self.max_query_k))
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in pred + ((rad, ids, dists, counts) if rad is not None else ()):  # as the pair's calls do
+                t.record_stream(stream)
+        return rc
+
+    def _exact_between(self, y, alias, kq, rad, pred):
+        """annhip_index_exact_query_between -> (ids, dists, counts); counts is written only with a radius."""
+        import torch
+        Q = y.shape[0]
+        ids = torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        if self.lib.annhip_index_exact_query_between(self.h, Q, y.data_ptr(), int(bool(alias)), kq,
+                                                     _ptr(rad, hold) if rad is not None else None, pred[0].data_ptr(),
+                                                     pred[1].data_ptr(), pred[2].data_ptr(), _ptr(ids, hold), _ptr(dists, hold),
+                                                     counts.data_ptr()) != 0:
+            raise ValueError("annhip_index_exact_query_between refused k=%d (k outside 1..1024 or larger than the rows on "
+                             "offer, no tags, or a resharded index)" % kq)
+        return ids, dists, counts
+
     def exact_query(self, y, alias=False, where=None, k=None):
         """annhip_index_exact_query: the exact k nearest of the index's (native) rows for y [Q,d], k = the index's k ->
         (ids int64 [Q,k], sq dists [Q,k]), ordered by (distance, id).  alias: query q leaves out point q.  ValueError where
@@ -860,10 +940,19 @@ class Index:
         shape or dtype and for an index without tags.
         k: None = the index's k, the calls above.  An integer: annhip_index_exact_query_k, the exact k nearest ->
         [Q,k] tensors; ValueError for a bool or a non-integer and where the library refuses (k outside 1..1024,
-        k > n - alias, a resharded index, where= without tags)."""
+        k > n - alias, a resharded index, where= without tags).  where = (qmask, qlo, qhi) as in query():
+        annhip_index_exact_query_between, with or without k=."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
+        if where is not None and isinstance(where, (tuple, list)) and len(where) == 3:
+            kq = self.k if k is None else self._check_k(k)
+            if kq < 1:
+                raise ValueError("exact_query(k=...): k must be in 1..1024")
+            pred = _where_dev(where, Q, y.device)
+            if not self.has_tags:
+                raise ValueError("exact_query(where=...): the index has no tags (Index.set_tags)")
+            return self._exact_between(y, alias, kq, None, pred)[:2]
         if k is not None:
             k = self._check_k(k)
             if k < 1:
@@ -962,11 +1051,15 @@ class Index:
             raise ValueError("query_radius: k must be at least 1")
         rad = _radius_dev(radius, Q, y.dtype, y.device)
         qm = qv = None
-        if where is not None:
-            qm, qv = _where_dev(where, Q, y.device)
+        pred = _where_dev(where, Q, y.device) if where is not None else None
         ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
         dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
         counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        if pred is not None and len(pred) == 3:  # (qmask, qlo, qhi): annhip_query_between
+            self._between(y, alias, k, rad, pred, ids, dists, counts, ws, stream)
+            return ids, dists, counts
+        if pred is not None:
+            qm, qv = pred
         if stream is not None and torch.cuda.current_stream(y.device) != stream:
             stream.wait_stream(torch.cuda.current_stream(y.device))  # the radius, predicate and output arrays were made on that one
         hold = torch.empty((1,), dtype=torch.int64, device=y.device)
@@ -996,7 +1089,10 @@ class Index:
         rad = _radius_dev(radius, Q, y.dtype, y.device)
         qm = qv = None
         if where is not None:
-            qm, qv = _where_dev(where, Q, y.device)
+            pred = _where_dev(where, Q, y.device)
+            if len(pred) == 3:  # (qmask, qlo, qhi): annhip_index_exact_query_between
+                return self._exact_between(y, alias, k, rad, pred)
+            qm, qv = pred
         ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
         dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
         counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)

@@ -64,6 +64,30 @@ __device__ __forceinline__ FT ft_inf() {
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// The tag predicate of one query (ann_tag_kernels.h): qlo <= (t & qmask) <= qhi in unsigned arithmetic, held as
+// (qm, lo, span = qhi - qlo) so that the test is one subtract and one unsigned compare: a masked word below lo wraps to
+// more than 2^32 - 1 - lo >= span.  qlo > qhi matches nothing and is canonicalised on load to (0, 1, 0), never to a
+// wrapped span.  The pair form (mask, value) passes its value array for both bounds: span = 0.  {0, 0, 0} matches every
+// word.  x must be wave-uniform (every caller's is: a workgroup's or a wave's query): the three words are scalar loads and
+// stay in scalar registers.  The readfirstlane says so to the compiler, which otherwise turns lo <= hi ? hi - lo : 0 into a
+// saturating subtract -- a vector instruction, i.e. one vector register per query in kernels that have none to spare
+// (exact_scan_kernel's EX_TAGS form: the f64 d = 80 instance spilled four).
+struct TagPred {
+  u32 qm, lo, span;
+};
+__device__ __forceinline__ TagPred tag_pred(const u32 *__restrict__ qmask, const u32 *__restrict__ qlo, const u32 *__restrict__ qhi, u32 x) {
+  const u32 m = qmask[x], lo = qlo[x], hi = qhi[x];
+  const bool some = lo <= hi;
+  TagPred p;
+  p.qm = __builtin_amdgcn_readfirstlane(some ? m : 0u);
+  p.lo = __builtin_amdgcn_readfirstlane(some ? lo : 1u);
+  p.span = __builtin_amdgcn_readfirstlane(some ? hi - lo : 0u);
+  return p;
+}
+__device__ __forceinline__ bool tag_match(u32 t, u32 qm, u32 lo, u32 span) { return ((t & qm) - lo) <= span; }
+__device__ __forceinline__ bool tag_match(u32 t, const TagPred &p) { return tag_match(t, p.qm, p.lo, p.span); }
+
 // number of set bits of a 64-bit ballot below this lane
 __device__ __forceinline__ u32 mask_rank(u64 m) {
   return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0));

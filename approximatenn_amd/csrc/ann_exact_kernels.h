@@ -201,7 +201,7 @@ __device__ __forceinline__ bool ex_tile_allows(const u32 *tbits, u32 t0, u32 id)
 // exact_shape's smem_of.
 struct ExValidArgs {
   const u32 *tags, *bits;  // EX_BITS: bits (read through the kernels' `allow`); EX_TAGS: tags, and bits or NULL
-  const u32 *qmask, *qvalue;
+  const u32 *qmask, *qlo, *qhi;  // EX_TAGS: qlo <= (tag & qmask) <= qhi; the pair form passes its value array twice
 };
 
 // the validity words of tile [t0, t0 + rows) -> LDS.  A macro: the kernels' loops as they stand, not an inlined function
@@ -219,7 +219,7 @@ struct ExValidArgs {
 // EX_BITS: a row whose bit is clear is never a survivor, and a wave pass without an allowed row is not scored at all.
 // Where the next tile travels through registers, so does its bitmap: one word per thread (such a tile has at most 128
 // rows per wave, hence fewer words than the workgroup has threads).
-// EX_TAGS: each of the wave's ANN_EX_QB queries applies its own (mask, value) in pass[i]; a wave pass in which no row
+// EX_TAGS: each of the wave's ANN_EX_QB queries applies its own (mask, lo, hi) in pass[i]; a wave pass in which no row
 // matches any of the four is not scored at all.  Where the next tile travels through registers, so do its tags: one word
 // per thread (the host prefetches only where a tile has no more rows than the workgroup has threads, i.e. rows of 32
 // bytes at least).  That word takes the place of the prefetched bitmap word -- these kernels have no register to spare
@@ -251,16 +251,17 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
   S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
   const ExLanes<D> ln(d, lane);
   VT a[ANN_EX_QB][C];
-  u32 qm[ANN_EX_QB], qv[ANN_EX_QB];  // wave-uniform: scalar registers
+  u32 qm[ANN_EX_QB], ql[ANN_EX_QB], qs[ANN_EX_QB];  // TagPred (mask, lo, span) of each query; wave-uniform: scalar registers
 #pragma unroll
   for (int i = 0; i < ANN_EX_QB; i++) {
     const u32 q = qbase + i < qend ? qbase + i : qend - 1;  // loads stay inside y; the result is never admitted
     const FT *yq = A.y + (size_t)q * d;
     if constexpr (V == EX_TAGS) {
       const u32 qu = __builtin_amdgcn_readfirstlane(q);  // (the wave index is uniform, which the compiler cannot see)
-      qm[i] = G.qmask[qu], qv[i] = G.qvalue[qu];         // scalar loads into scalar registers
+      const TagPred tp = tag_pred(G.qmask, G.qlo, G.qhi, qu);  // scalar loads into scalar registers
+      qm[i] = tp.qm, ql[i] = tp.lo, qs[i] = tp.span;
     } else {
-      qm[i] = 0, qv[i] = 0;
+      qm[i] = 0, ql[i] = 0, qs[i] = 0;
     }
 #pragma unroll
     for (int c = 0; c < C; c++) {
@@ -305,7 +306,8 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
         allowed = act && ((V == EX_TAGS && !bits) || ex_tile_allows(tbits, t0, t0 + r));
         if constexpr (V == EX_TAGS) {
           const u32 tg = ttags[act ? r : r0];
-          allowed = allowed && ((tg & qm[0]) == qv[0] || (tg & qm[1]) == qv[1] || (tg & qm[2]) == qv[2] || (tg & qm[3]) == qv[3]);
+          allowed = allowed && (tag_match(tg, qm[0], ql[0], qs[0]) || tag_match(tg, qm[1], ql[1], qs[1]) ||
+                                tag_match(tg, qm[2], ql[2], qs[2]) || tag_match(tg, qm[3], ql[3], qs[3]));
         }
         if (!__ballot(allowed)) continue;  // wave-uniform: no row of this pass can survive for any of the four queries
       }
@@ -330,7 +332,7 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void exact_scan_kernel(ExArgs
       }
 #pragma unroll
       for (int i = 0; i < ANN_EX_QB; i++)
-        pass[i] = head && (V != EX_TAGS || (tg & qm[i]) == qv[i]) && key_less(key[i], S.tau[i]) && !(A.self && id == qbase + i);
+        pass[i] = head && (V != EX_TAGS || tag_match(tg, qm[i], ql[i], qs[i])) && key_less(key[i], S.tau[i]) && !(A.self && id == qbase + i);
       if (__ballot(pass[0] || pass[1] || pass[2] || pass[3])) {
         S.offer<0>(pass[0], key[0]);
         S.offer<1>(pass[1], key[1]);
@@ -444,12 +446,13 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void exact_scan_generic_kern
 #define ANN_EX_GEN_SCAN(I)                                                                                   \
   if (qbase + (I) < qend) {                                                                                  \
     const u32 qu = __builtin_amdgcn_readfirstlane(qbase + (I));                                              \
-    const u32 qm = V == EX_TAGS ? G.qmask[qu] : 0, qv = V == EX_TAGS ? G.qvalue[qu] : 0;                     \
+    TagPred tp{0, 0, 0};                                                                                     \
+    if constexpr (V == EX_TAGS) tp = tag_pred(G.qmask, G.qlo, G.qhi, qu);                                    \
     ANN_EX_GEN_QUERY(qbase + (I), {                                                                          \
       const u32 id = t0 + r0 + lane;                                                                         \
       bool act;                                                                                              \
       if constexpr (V == EX_TAGS) {                                                                          \
-        act = lane < np && (ttags[r0 + lane] & qm) == qv && (!bits || ex_tile_allows(tbits, t0, id));        \
+        act = lane < np && tag_match(ttags[r0 + lane], tp) && (!bits || ex_tile_allows(tbits, t0, id));      \
       } else {                                                                                               \
         act = lane < np;                                                                                     \
         if constexpr (V == EX_BITS) act = act && ex_tile_allows(tbits, t0, id);                              \

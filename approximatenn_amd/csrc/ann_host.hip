@@ -1302,10 +1302,12 @@ static size_t stage1_probe_lds_bytes(const QParams &P, int W, int K1, int cap, i
 }
 
 // The per-query tag predicate of one annhip_query_tagged call (ann_tag_kernels.h): the rows' tag words and the batch's
-// (mask, value) arrays, all on the device.
+// (mask, lo, hi) arrays, all on the device: qlo <= (tag & qmask) <= qhi.  The pair form (mask, value) is qlo = qhi = its
+// value array (tag_pair), the range form (annhip_query_between) gives the three apart; the kernels are the same.
 struct TagQuery {
-  const u32 *tags, *qmask, *qvalue;
+  const u32 *tags, *qmask, *qlo, *qhi;
 };
+static TagQuery tag_pair(const u32 *tags, const u32 *qmask, const u32 *qvalue) { return TagQuery{tags, qmask, qvalue, qvalue}; }
 
 // Stage 1 of fixed mode over 1 + ds + pb (pb - 1) / 2 buckets per try (pb = 0: the plain 1 + ds, no ranked bits), for
 // every family that walks the (try, mask) runs (stage1_fixed_body in ann_probe_kernels.h and its two copies): with a radius
@@ -1324,7 +1326,7 @@ static void launch_stage1_fixed(annhip_index *ix, const QParams &P, size_t Q, co
   if (env().s1_waves) W = env().s1_waves;
   const int K1 = P.k + 1, cap = stage1_cap(W, K1);
   const size_t smem = stage1_probe_lds_bytes(P, W, K1, cap, pb);
-  const u32 *tags = tq ? tq->tags : NULL, *qmask = tq ? tq->qmask : NULL, *qvalue = tq ? tq->qvalue : NULL;
+  const u32 *tags = tq ? tq->tags : NULL, *qmask = tq ? tq->qmask : NULL, *qlo = tq ? tq->qlo : NULL, *qhi = tq ? tq->qhi : NULL;
   EventPair ev;
   if (ix->profile) ev = s1_prof_begin(ix, s);
   with_value(QueryLayouts{}, layout_code(P.d), [&](auto dd) {
@@ -1337,11 +1339,11 @@ static void launch_stage1_fixed(annhip_index *ix, const QParams &P, size_t Q, co
         if (radius) {
           allow_lds(stage1_radius_kernel<D, SG, RT>, smem);
           hipLaunchKernelGGL((stage1_radius_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, radius,
-                             tags, bits, qmask, qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
+                             tags, bits, qmask, qlo, qhi, K1, cap, cand_d, cand_i, nvt, nvo);
         } else if (tq) {
           allow_lds(stage1_tag_kernel<D, SG, RT>, smem);
           hipLaunchKernelGGL((stage1_tag_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, tags, bits,
-                             qmask, qvalue, K1, cap, cand_d, cand_i, nvt, nvo);
+                             qmask, qlo, qhi, K1, cap, cand_d, cand_i, nvt, nvo);
         } else if (bits) {
           allow_lds(stage1_filter_kernel<D, SG, RT>, smem);
           hipLaunchKernelGGL((stage1_filter_kernel<D, SG, RT>), grid, block, smem, s, P, y, alias, codes, pbits, pb, rpt, bits, K1,
@@ -1535,7 +1537,7 @@ static bool stage2_select_with_fallback(const QParams &P, size_t Q, const FT *y,
         if (tq) {
           allow_lds((stage2_tag_kernel<D, TT, RT>), smem);
           hipLaunchKernelGGL((stage2_tag_kernel<D, TT, RT>), dim3((unsigned)nq), dim3(64 * W), smem, s, P, (int)Q, y, alias,
-                             top_i, top_d, tq->tags, filter, tq->qmask, tq->qvalue, P2, K1, cap, out, out_d, fl, d_fcount,
+                             top_i, top_d, tq->tags, filter, tq->qmask, tq->qlo, tq->qhi, P2, K1, cap, out, out_d, fl, d_fcount,
                              exact_total, rows_ctr, xbase);
           return;
         }
@@ -1931,7 +1933,7 @@ extern "C" long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void
     fprintf(stderr, "annhip_query_tagged: %s\n", why);
     return -2;
   }
-  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
   return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
 }
 
@@ -1987,7 +1989,7 @@ static void launch_stage2_kq(const QParams &P, size_t Q, const FT *y, int alias,
       allow_lds((stage2_kq_kernel<D, size_t, RT>), smem);
       hipLaunchKernelGGL((stage2_kq_kernel<D, size_t, RT>), dim3((unsigned)Q), dim3(64 * W), smem, s, P, y, alias, top_i, top_d,
                          (int)kq, tq ? tq->tags : (const u32 *)NULL, filter, tq ? tq->qmask : (const u32 *)NULL,
-                         tq ? tq->qvalue : (const u32 *)NULL, K1, cap, out_ids, out_d, rows_ctr);
+                         tq ? tq->qlo : (const u32 *)NULL, tq ? tq->qhi : (const u32 *)NULL, K1, cap, out_ids, out_d, rows_ctr);
     });
   });
   HIPCHECK(hipGetLastError());
@@ -2053,7 +2055,7 @@ extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip
     fprintf(stderr, "annhip_query_k: %s\n", why);
     return -2;
   }
-  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
   return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, tagged ? &tq : NULL, NULL, ids_dev,
                       dists_dev, NULL);
 }
@@ -2085,9 +2087,34 @@ extern "C" long annhip_query_radius(annhip_index *ix, annhip_workspace *ws, void
     fprintf(stderr, "annhip_query_radius: %s\n", why);
     return -2;
   }
-  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
   return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kcap, tagged ? &tq : NULL,
                       reinterpret_cast<const FT *>(radius_dev), ids_dev, dists_dev, counts_dev);
+}
+
+// Contract: include/ann_hip.h.  The range form of annhip_query_k (radius_dev == NULL) and annhip_query_radius: the same
+// launchers with the two bounds apart.  With the index's own k and no radius it takes annhip_query_tagged's path, the
+// stage1_tag / stage2_tag kernels.  A refusal launches nothing and leaves the outputs untouched.
+extern "C" long annhip_query_between(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev,
+                                     int alias, size_t kq, const ftype *radius_dev, const uint32_t *qmask_dev,
+                                     const uint32_t *qlo_dev, const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev,
+                                     uint32_t *counts_dev) {
+  const bool own_k = !radius_dev && kq == (size_t)ix->k;
+  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
+                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                    : !qmask_dev || !qlo_dev || !qhi_dev ? "qmask_dev, qlo_dev and qhi_dev must all be given"
+                    : !ix->tags ? "the index has no tags (annhip_index_set_tags)"
+                    : radius_dev && !ids_dev ? "ids_dev must be given"
+                    : !own_k && !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_query_between: %s\n", why);
+    return -2;
+  }
+  const TagQuery tq{ix->tags, qmask_dev, qlo_dev, qhi_dev};
+  annhip_workspace &w = ws ? *ws : ix->ws;
+  if (own_k) return query_impl(ix, w, (hipStream_t)hip_stream, ycnt, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
+  return query_k_impl(ix, w, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, &tq, reinterpret_cast<const FT *>(radius_dev), ids_dev,
+                      dists_dev, counts_dev);
 }
 
 extern "C" int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev,
@@ -2731,7 +2758,18 @@ extern "C" int annhip_exact_knn_tagged(size_t n, size_t d, size_t k, const ftype
                                        ftype *dists_dev) {
   if (!tags_dev || !qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
   if (const int rc = exact_check(n, d, k, self)) return rc;
-  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, EX_TAGS, ExValidArgs{tags_dev, bits_dev, qmask_dev, qvalue_dev},
+  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, EX_TAGS, ExValidArgs{tags_dev, bits_dev, qmask_dev, qvalue_dev, qvalue_dev},
+                    ids_dev, dists_dev);
+}
+
+// Contract: include/ann_hip.h.  annhip_exact_knn_tagged's scan (the EX_TAGS form) with the two bounds apart.
+extern "C" int annhip_exact_knn_between(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev,
+                                        int self, const uint32_t *tags_dev, const uint32_t *bits_dev,
+                                        const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                                        size_t *ids_dev, ftype *dists_dev) {
+  if (!tags_dev || !qmask_dev || !qlo_dev || !qhi_dev) return exact_refuse("tags_dev, qmask_dev, qlo_dev and qhi_dev must all be given");
+  if (const int rc = exact_check(n, d, k, self)) return rc;
+  return exact_scan(n, d, k, points_dev, ycnt, y_dev, self, EX_TAGS, ExValidArgs{tags_dev, bits_dev, qmask_dev, qlo_dev, qhi_dev},
                     ids_dev, dists_dev);
 }
 
@@ -2771,7 +2809,8 @@ static void launch_tail_merge(annhip_index *ix, size_t Q, const FT *y, int alias
   const ExValid valid = tq ? EX_TAGS : ix->filter ? EX_BITS : EX_ALL;
   TailArgs A;
   A.tail = ix->d_tail + skip * d, A.y = y, A.in_ids = in_ids, A.in_d = in_d, A.out_ids = ids, A.out_d = dists;
-  A.bits = ix->filter, A.tags = tq ? tq->tags : NULL, A.qmask = tq ? tq->qmask : NULL, A.qvalue = tq ? tq->qvalue : NULL;
+  A.bits = ix->filter, A.tags = tq ? tq->tags : NULL, A.qmask = tq ? tq->qmask : NULL, A.qlo = tq ? tq->qlo : NULL,
+  A.qhi = tq ? tq->qhi : NULL;
   A.scored = scored;
   A.n = (u32)(ix->n + skip), A.m = (u32)(ix->tail_m - skip), A.Q = (u32)Q;
   A.d = (int)d, A.k = (int)k, A.kin = (int)kin, A.self = alias ? 1 : 0;
@@ -2817,7 +2856,8 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
   const ExValid valid = tq ? EX_TAGS : ix->filter ? EX_BITS : EX_ALL;
   TailHashArgs A;
   A.t.tail = ix->d_tail, A.t.y = y, A.t.in_ids = ids, A.t.in_d = dists, A.t.out_ids = ids, A.t.out_d = dists;
-  A.t.bits = ix->filter, A.t.tags = tq ? tq->tags : NULL, A.t.qmask = tq ? tq->qmask : NULL, A.t.qvalue = tq ? tq->qvalue : NULL;
+  A.t.bits = ix->filter, A.t.tags = tq ? tq->tags : NULL, A.t.qmask = tq ? tq->qmask : NULL, A.t.qlo = tq ? tq->qlo : NULL,
+  A.t.qhi = tq ? tq->qhi : NULL;
   A.t.scored = scored;
   A.t.n = (u32)ix->n, A.t.m = (u32)ix->tail_m, A.t.Q = (u32)Q;
   A.t.d = (int)d, A.t.k = (int)k, A.t.kin = (int)k, A.t.self = 0, A.t.tile_rows = 0, A.t.prefetch = 0;
@@ -2895,21 +2935,22 @@ extern "C" int annhip_index_hash_tail(annhip_index *ix) {
 }
 
 // The three exact scans of an index: over the built rows as before, then -- where rows have been appended -- the tail's
-// scan merged in.  kq = the k of the call.  qmask_dev == NULL: untagged.
+// scan merged in.  kq = the k of the call.  qmask_dev == NULL: untagged; the pair form passes its value array for both bounds.
 static int index_exact(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq, const uint32_t *qmask_dev,
-                       const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev) {
+                       const uint32_t *qlo_dev, const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev) {
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if (qmask_dev && !ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
   const ftype *pts = reinterpret_cast<const ftype *>(ix->d_points);
   auto built = [&](size_t k, size_t *ids, ftype *dists) {
     if (!qmask_dev) return annhip_exact_knn_filtered(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->filter, ids, dists);
-    return annhip_exact_knn_tagged(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->tags, ix->filter, qmask_dev, qvalue_dev, ids, dists);
+    return annhip_exact_knn_between(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->tags, ix->filter, qmask_dev, qlo_dev, qhi_dev, ids,
+                                    dists);
   };
   if (!ix->tail_m) return built(kq, ids_dev, dists_dev);
   if (const int rc = exact_check(n_total(ix), ix->d, kq, alias)) return rc;
   if (!ycnt) return 0;
   const size_t kin = std::min(kq, ix->n - (alias && ix->n ? 1 : 0));  // what the built rows can fill
-  const TagQuery tq{ix->tags, qmask_dev, qvalue_dev};
+  const TagQuery tq{ix->tags, qmask_dev, qlo_dev, qhi_dev};
   const FT *y = reinterpret_cast<const FT *>(y_dev);
   FT *dd = reinterpret_cast<FT *>(dists_dev);
   int rc = 0;
@@ -2931,7 +2972,7 @@ static int index_exact(annhip_index *ix, size_t ycnt, const ftype *y_dev, int al
 
 extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t *ids_dev,
                                         ftype *dists_dev) {
-  return index_exact(ix, ycnt, y_dev, alias, ix->k, NULL, NULL, ids_dev, dists_dev);
+  return index_exact(ix, ycnt, y_dev, alias, ix->k, NULL, NULL, NULL, ids_dev, dists_dev);
 }
 
 extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
@@ -2940,7 +2981,7 @@ extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, co
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
   if (!qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
-  return index_exact(ix, ycnt, y_dev, alias, ix->k, qmask_dev, qvalue_dev, ids_dev, dists_dev);
+  return index_exact(ix, ycnt, y_dev, alias, ix->k, qmask_dev, qvalue_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
 // Contract: include/ann_hip.h.  The three exact scans with a k of the call's own; their refusals.
@@ -2949,7 +2990,7 @@ extern "C" int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const f
                                           ftype *dists_dev) {
   if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
   if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
-  return index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qvalue_dev, ids_dev, dists_dev);
+  return index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qvalue_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
 // Contract: include/ann_hip.h.  annhip_index_exact_query_k's path, then the trim (ann_radius_kernels.h): the ground truth of
@@ -2962,6 +3003,23 @@ extern "C" int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, co
   if (!radius_dev || !ids_dev || !dists_dev) return exact_refuse("radius_dev, ids_dev and dists_dev must all be given");
   if (const int rc = annhip_index_exact_query_k(ix, ycnt, y_dev, alias, kcap, qmask_dev, qvalue_dev, ids_dev, dists_dev)) return rc;
   launch_radius_trim(ycnt, kcap, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
+                     counts_dev, 0);
+  HIPCHECK(hipStreamSynchronize(0));
+  return 0;
+}
+
+// Contract: include/ann_hip.h.  annhip_index_exact_query_k's scans under the range predicate, then -- with a radius --
+// annhip_index_exact_query_radius' trim.  Synchronous, on the null stream.
+extern "C" int annhip_index_exact_query_between(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
+                                                const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qlo_dev,
+                                                const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev,
+                                                uint32_t *counts_dev) {
+  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
+  if (!qmask_dev || !qlo_dev || !qhi_dev) return exact_refuse("qmask_dev, qlo_dev and qhi_dev must all be given");
+  if (radius_dev && (!ids_dev || !dists_dev)) return exact_refuse("radius_dev needs ids_dev and dists_dev");
+  if (const int rc = index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qlo_dev, qhi_dev, ids_dev, dists_dev)) return rc;
+  if (!radius_dev) return 0;
+  launch_radius_trim(ycnt, kq, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
                      counts_dev, 0);
   HIPCHECK(hipStreamSynchronize(0));
   return 0;

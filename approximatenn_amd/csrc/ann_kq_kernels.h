@@ -8,9 +8,9 @@
 //   row of query x   kq + kq * kg slots: slot j < kq is stage-1 result j with the distance it already has, slot
 //                    kq + p * kg + z is graph[top[p]][z], z < kg.  A pad among the stage-1 results, (n, +inf), has no
 //                    neighbours: it contributes nothing.
-//   ok               id < n, not x itself when aliased, bit id of `bits` when bits != NULL, (tags[id] & qmask[x]) ==
-//                    qvalue[x] when tags != NULL.  Tested where an id ENTERS the wave's LDS list: a rejected row is
-//                    never fetched.  NULL or not is wave-uniform: one branch each, no template axis.
+//   ok               id < n, not x itself when aliased, bit id of `bits` when bits != NULL, qlo[x] <= (tags[id] &
+//                    qmask[x]) <= qhi[x] when tags != NULL (the pair form passes qvalue twice).  Tested where an id
+//                    ENTERS the wave's LDS list: a rejected row is never fetched.  NULL or not is wave-uniform: one branch each, no template axis.
 //   output           the kq smallest distinct (distance, id) keys, ascending, (n, +inf) where fewer exist.
 //
 // The waves split the row in runs of 64 slots.  A lane needs (p, z) of its slot in every pass; dividing by the run-time
@@ -33,15 +33,15 @@ template <int D, typename IdOut, typename RT>
 __global__ __launch_bounds__(256) void stage2_kq_kernel(QParams P, const FT *__restrict__ y, int alias,
                                                         const u32 *__restrict__ top_id, const FT *__restrict__ top_dist, int kq,
                                                         const u32 *__restrict__ tags, const u32 *__restrict__ bits,
-                                                        const u32 *__restrict__ qmask, const u32 *__restrict__ qvalue, int K1,
+                                                        const u32 *__restrict__ qmask, const u32 *__restrict__ qlo, const u32 *__restrict__ qhi, int K1,
                                                         int cap, IdOut *__restrict__ out_ids, FT *__restrict__ out_dist,
                                                         unsigned long long *__restrict__ rows_done) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
   const u32 x = blockIdx.x;
   const int kg = P.k;
-  u32 qm = 0, qv = 0;  // wave-uniform: this query's predicate, read once
-  if (tags) qm = qmask[x], qv = qvalue[x];
+  TagPred tp{0, 0, 0};  // wave-uniform: this query's predicate, read once
+  if (tags) tp = tag_pred(qmask, qlo, qhi, x);
   unsigned char *sp = smem;
   Key *kbuf_all = reinterpret_cast<Key *>(sp);   sp += sizeof(Key) * (size_t)W * cap;
   Key *kout_all = reinterpret_cast<Key *>(sp);   sp += sizeof(Key) * (size_t)W * K1;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void stage2_kq_kernel(QParams P, const FT *__r
           id = P.graph[(size_t)parent * kg + z];
           ok = id < P.n && !(alias && id == x);
           if (ok && bits) ok = filter_allows(bits, id);
-          if (ok && tags) ok = (tags[id] & qm) == qv;
+          if (ok && tags) ok = tag_match(tags[id], tp);
         }
       }
     }

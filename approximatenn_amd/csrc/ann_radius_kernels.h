@@ -24,8 +24,8 @@
 #include "ann_kq_kernels.h"
 
 // id < n (the caller's test).  The two loads are independent of each other where both tests apply.
-__device__ __forceinline__ bool radius_allows(const u32 *__restrict__ tags, const u32 *__restrict__ bits, u32 qm, u32 qv, u32 id) {
-  if (tags) return tag_allows(tags, bits, qm, qv, id);
+__device__ __forceinline__ bool radius_allows(const u32 *__restrict__ tags, const u32 *__restrict__ bits, const TagPred &tp, u32 id) {
+  if (tags) return tag_allows(tags, bits, tp, id);
   if (bits) return filter_allows(bits, id);
   return true;
 }
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT 
                                                             const unsigned char *__restrict__ pbits, int pb, u32 rpt,
                                                             const FT *__restrict__ radius,
                                                             const u32 *__restrict__ tags, const u32 *__restrict__ bits,
-                                                            const u32 *__restrict__ qmask, const u32 *__restrict__ qvalue,
+                                                            const u32 *__restrict__ qmask, const u32 *__restrict__ qlo, const u32 *__restrict__ qhi,
                                                             int K1, int cap, FT *__restrict__ cand_dist,
                                                             u32 *__restrict__ cand_id, u32 *__restrict__ nv_tot,
                                                             u32 *__restrict__ nv_own) {
@@ -78,8 +78,8 @@ __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT 
   const u32 **rptr = rptr_all + (size_t)w * ANN_WAVE;
 
   const u32 x = blockIdx.x;
-  u32 qm = 0, qv = 0;  // wave-uniform: this query's predicate and radius, read once
-  if (tags) qm = qmask[x], qv = qvalue[x];
+  TagPred tp{0, 0, 0};  // wave-uniform: this query's predicate and radius, read once
+  if (tags) tp = tag_pred(qmask, qlo, qhi, x);
   const Key tau0 = radius_tau(radius[x]);
   for (int i = threadIdx.x; i < P.T; i += blockDim.x) {
     tries[i] = P.tries[i];
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT 
           }
           id = rptr[lo_][e - pref[lo_]];
         }
-        const bool own = id < P.n && radius_allows(tags, bits, qm, qv, id);
+        const bool own = id < P.n && radius_allows(tags, bits, tp, id);
         const u64 mm = __ballot(own);
         if (own) list[cnt + mask_rank(mm)] = id;
         cnt += __popcll(mm);
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void stage1_radius_kernel(QParams P, const FT 
         const u32 id = z < tr.pm ? row[z] : ANN_ID_NONE;
         const bool ok = id < P.n && !(alias && id == x);
         // (the aliased query itself is counted when it is valid, as in the segment path; probe_gather drops it)
-        const bool own = id < P.n && id >= P.lo && id < P.hi && radius_allows(tags, bits, qm, qv, id);
+        const bool own = id < P.n && id >= P.lo && id < P.hi && radius_allows(tags, bits, tp, id);
         vtot += __popcll(__ballot(ok));
         const u64 mm = __ballot(own);
         if (own) list[cnt + mask_rank(mm)] = id;

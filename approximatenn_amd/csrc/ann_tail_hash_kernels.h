@@ -108,7 +108,7 @@ __device__ __forceinline__ void thash_load_query(const TailHashArgs &A, const Th
 // cj[0..cnt) / ct: candidates as found -> cj[0..return): those that hit in no earlier try and are valid for the query
 template <int V>
 __device__ __forceinline__ int thash_reject(const TailHashArgs &A, const ThashWave &L, int cnt, const u32 *__restrict__ bits,
-                                            const u32 *__restrict__ tags, u32 qm, u32 qv) {
+                                            const u32 *__restrict__ tags, const TagPred &tp) {
   const int lane = lane_id();
   int ns = 0;
   for (int e0 = 0; e0 < cnt; e0 += ANN_WAVE) {
@@ -120,7 +120,7 @@ __device__ __forceinline__ int thash_reject(const TailHashArgs &A, const ThashWa
     if constexpr (V != EX_ALL) {
       const u32 id = A.t.n + j;
       if (ok && bits) ok = (bits[id >> 5] >> (id & 31)) & 1u;
-      if (V == EX_TAGS && ok) ok = (tags[id] & qm) == qv;
+      if (V == EX_TAGS && ok) ok = tag_match(tags[id], tp);
     }
     const u64 mm = __ballot(ok);
     wave_lds_sync();  // the pass has read its entries; ns + rank <= e
@@ -135,7 +135,7 @@ __device__ __forceinline__ int thash_reject(const TailHashArgs &A, const ThashWa
 // row numbers into the chunk (stage1_probe_kernel's idiom); score(ns) runs over cj[0..ns) whenever the chunk has filled.
 template <int V, typename Score>
 __device__ __forceinline__ void thash_enumerate(const TailHashArgs &A, const ThashWave &L, u32 q, const u32 *__restrict__ bits,
-                                                const u32 *__restrict__ tags, u32 qm, u32 qv, Score &&score) {
+                                                const u32 *__restrict__ tags, const TagPred &tp, Score &&score) {
   const int lane = lane_id();
   const u32 ds = (u32)A.ds, rpt = 1u + ds + (u32)(A.pb * (A.pb - 1) / 2), runs = (u32)A.T * rpt;
   const u32 stride = (1u << ds) + 1u;
@@ -169,14 +169,14 @@ __device__ __forceinline__ void thash_enumerate(const TailHashArgs &A, const Tha
       cnt += take, done += take;
       if (cnt == ANN_THASH_CHUNK) {
         wave_lds_sync();
-        score(thash_reject<V>(A, L, cnt, bits, tags, qm, qv));
+        score(thash_reject<V>(A, L, cnt, bits, tags, tp));
         cnt = 0;
       }
     }
     wave_lds_sync();  // pref / rst / rtry are rewritten by the next pass
   }
   wave_lds_sync();
-  if (cnt) score(thash_reject<V>(A, L, cnt, bits, tags, qm, qv));
+  if (cnt) score(thash_reject<V>(A, L, cnt, bits, tags, tp));
 }
 
 // LDS of one workgroup: per wave one selection buffer (cap keys + k keys of scratch), then the ThashWave words
@@ -201,8 +201,8 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_hash_merge_kernel(T
     if constexpr (D > 0) a[c] = reinterpret_cast<const VT *>(yq)[ln.p + c * ln.oc];
     else a[c] = oc_load_chunk<D, false>(yq, ln.p + c * ln.oc, d);
   }
-  u32 qm = 0, qv = 0;
-  if constexpr (V == EX_TAGS) qm = A.t.qmask[q], qv = A.t.qvalue[q];
+  TagPred tp{0, 0, 0};
+  if constexpr (V == EX_TAGS) tp = tag_pred(A.t.qmask, A.t.qlo, A.t.qhi, q);
   const u32 *__restrict__ bits = V == EX_ALL ? (const u32 *)NULL : A.t.bits;
   thash_load_query(A, L, q);
   tail_seed<0>(S, A.t, q, true);
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_hash_merge_kernel(T
     }
     wave_lds_sync();  // the chunk is refilled
   };
-  thash_enumerate<V>(A, L, q, bits, A.t.tags, qm, qv, score);
+  thash_enumerate<V>(A, L, q, bits, A.t.tags, tp, score);
   tail_store<0>(S, A.t, q, true);
   if (A.t.scored && lane == 0 && nsc) atomicAdd(&A.t.scored[(blockIdx.x & 63u) * 8u], (unsigned long long)nsc);
 }
@@ -265,8 +265,8 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_hash_merge_generic
   ExSel S;
   S.init(kbase, kbase + A.t.cap, A.t.cap, A.t.k, q, A.t.Q);
   const u32 *__restrict__ tags = A.t.tags, *__restrict__ bits = A.t.bits;
-  u32 qm = 0, qv = 0;
-  if (tags) qm = A.t.qmask[q], qv = A.t.qvalue[q];
+  TagPred tp{0, 0, 0};
+  if (tags) tp = tag_pred(A.t.qmask, A.t.qlo, A.t.qhi, q);
   for (int z = lane; z < d; z += ANN_WAVE) yq[z] = A.t.y[(size_t)q * d + z];
   thash_load_query(A, L, q);
   tail_seed<0>(S, A.t, q, true);
@@ -308,8 +308,8 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_hash_merge_generic
     }
     wave_lds_sync();  // the chunk is refilled
   };
-  if (tags) thash_enumerate<EX_TAGS>(A, L, q, bits, tags, qm, qv, score);
-  else thash_enumerate<EX_BITS>(A, L, q, bits, tags, qm, qv, score);
+  if (tags) thash_enumerate<EX_TAGS>(A, L, q, bits, tags, tp, score);
+  else thash_enumerate<EX_BITS>(A, L, q, bits, tags, tp, score);
   tail_store<0>(S, A.t, q, true);
   if (A.t.scored && lane == 0 && nsc) atomicAdd(&A.t.scored[(blockIdx.x & 63u) * 8u], (unsigned long long)nsc);
 }

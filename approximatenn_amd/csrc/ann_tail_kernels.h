@@ -28,7 +28,7 @@ struct TailArgs {
   size_t *out_ids;         // [Q][k]
   FT *out_d;
   const u32 *bits, *tags;  // over ids [0, n_total); NULL where the form does not test them
-  const u32 *qmask, *qvalue;
+  const u32 *qmask, *qlo, *qhi;  // the pair form: qlo = qhi = its value array
   unsigned long long *scored;  // profiling: (query, valid tail row) pairs, 64 padded shards; or NULL
   u32 n, m, Q;             // built rows, tail rows, queries
   int d, k, kin, self, tile_rows, cap, prefetch;
@@ -99,16 +99,17 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
   S.init(kbase, kbase + (size_t)ANN_EX_QB * A.cap, A.cap, A.k, qbase, qend);
   const ExLanes<D> ln(d, lane);
   VT a[ANN_EX_QB][C];
-  u32 qm[ANN_EX_QB], qv[ANN_EX_QB];  // wave-uniform: scalar registers
+  u32 qm[ANN_EX_QB], ql[ANN_EX_QB], qs[ANN_EX_QB];  // TagPred (mask, lo, span) of each query; wave-uniform: scalar registers
 #pragma unroll
   for (int i = 0; i < ANN_EX_QB; i++) {
     const u32 q = qbase + i < qend ? qbase + i : qend - 1;  // loads stay inside y; the result is never admitted
     const FT *yq = A.y + (size_t)q * d;
     if constexpr (V == EX_TAGS) {
       const u32 qu = __builtin_amdgcn_readfirstlane(q);
-      qm[i] = A.qmask[qu], qv[i] = A.qvalue[qu];
+      const TagPred tp = tag_pred(A.qmask, A.qlo, A.qhi, qu);
+      qm[i] = tp.qm, ql[i] = tp.lo, qs[i] = tp.span;
     } else {
-      qm[i] = 0, qv[i] = 0;
+      qm[i] = 0, ql[i] = 0, qs[i] = 0;
     }
 #pragma unroll
     for (int c = 0; c < C; c++) {
@@ -156,7 +157,8 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
         allowed = act && (!bits || ex_tile_allows(tbits, id0, id0 + r));
         if constexpr (V == EX_TAGS) {
           const u32 tg = ttags[act ? r : r0];
-          allowed = allowed && ((tg & qm[0]) == qv[0] || (tg & qm[1]) == qv[1] || (tg & qm[2]) == qv[2] || (tg & qm[3]) == qv[3]);
+          allowed = allowed && (tag_match(tg, qm[0], ql[0], qs[0]) || tag_match(tg, qm[1], ql[1], qs[1]) ||
+                                tag_match(tg, qm[2], ql[2], qs[2]) || tag_match(tg, qm[3], ql[3], qs[3]));
         }
         if (!__ballot(allowed)) continue;  // wave-uniform: no row of this pass can survive for any of the four queries
       }
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void tail_merge_kernel(TailAr
       }
 #pragma unroll
       for (int i = 0; i < ANN_EX_QB; i++) {
-        ok[i] = head && (V != EX_TAGS || (tg & qm[i]) == qv[i]) && !(A.self && id == qbase + i);
+        ok[i] = head && (V != EX_TAGS || tag_match(tg, qm[i], ql[i], qs[i])) && !(A.self && id == qbase + i);
         pass[i] = ok[i] && key_less(key[i], S.tau[i]);
       }
       if (A.scored) {  // wave-uniform; a query beyond the batch counts nothing
@@ -270,14 +272,11 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void tail_merge_generic_kern
     __syncthreads();
 #define ANN_TAIL_GEN_QUERY(I)                                                                                \
   if (qbase + (I) < qend) {                                                                                  \
-    u32 qm = 0, qv = 0;                                                                                      \
-    if (tags) {                                                                                              \
-      const u32 qu = __builtin_amdgcn_readfirstlane(qbase + (I));                                            \
-      qm = A.qmask[qu], qv = A.qvalue[qu];                                                                   \
-    }                                                                                                        \
+    TagPred tp{0, 0, 0};                                                                                     \
+    if (tags) tp = tag_pred(A.qmask, A.qlo, A.qhi, __builtin_amdgcn_readfirstlane(qbase + (I)));             \
     ANN_EX_GEN_QUERY(qbase + (I), {                                                                          \
       const u32 id = id0 + r0 + lane;                                                                        \
-      const bool act = lane < np && (!tags || (ttags[r0 + lane] & qm) == qv) &&                              \
+      const bool act = lane < np && (!tags || tag_match(ttags[r0 + lane], tp)) &&                            \
                        (!bits || ex_tile_allows(tbits, id0, id)) && !(A.self && id == qbase + (I));          \
       const Key key = key_make(act ? m[lane * d] : zero, id);                                                \
       wave_lds_sync(); /* m is rewritten by the next batch */                                                \

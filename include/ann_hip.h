@@ -127,7 +127,23 @@ int annhip_filter_pack(size_t n, const uint8_t *flags_dev, uint32_t *bits_dev, v
  * annhip_stream_*, annhip_sh_*, annhip_query_slice, query_gpu and parity mode take no predicate.
  * annhip_stats out[2] counts, for a tagged query, the ids handed to the gather: the matching (and allowed) valid ids over
  * the probed buckets, repeats across tries counted, the query itself counted when it matches.
- * (annhip_query_tagged is declared below, beside annhip_query_on, where the workspace type is known.) */
+ * (annhip_query_tagged is declared below, beside annhip_query_on, where the workspace type is known.)
+ * Range predicates on the tag word (annhip_query_between, annhip_index_exact_query_between, annhip_exact_knn_between;
+ * declared below, after the radius calls).  Every query carries a (mask, lo, hi) triple (uint32_t qmask[ycnt], qlo[ycnt],
+ * qhi[ycnt]) and row i competes for query q iff qlo[q] <= (tags[i] & qmask[q]) <= qhi[q], both compares UNSIGNED 32-bit: a
+ * tag word with bit 31 set is large, not negative.  With fields packed high to low one interval is equality on the upper
+ * fields and a range on the lowest: tenant in bits 16-27, day in bits 0-15, mask 0x0FFFFFFF, lo = tenant << 16 | day_a,
+ * hi = tenant << 16 | day_b is "this tenant, this window".  The identities, all bit for bit on ids and distances:
+ *   qlo[q] == qhi[q]       the row of the pair-form call (annhip_query_tagged, annhip_query_k, annhip_query_radius,
+ *                          annhip_exact_knn_tagged, ...) with qvalue = qlo;
+ *   (qmask, qlo, qhi) = (0, 0, 0) and (m, 0, 0xFFFFFFFF)   the row of the untagged call, and the same number of rows
+ *                          handed to the gather (annhip_stats out[2]);
+ *   qlo[q] > qhi[q]        matches nothing (the interval never wraps); so does qlo[q] > qmask[q], which no masked word
+ *                          can reach: all pads.
+ * Everything else is the pair form's: the test happens before a row is fetched; the index's allow list is ANDed in; the
+ * alias rule, annhip_index_set_probe, annhip_index_set_rows, workspaces and streams, a k of the call's own, a radius, the
+ * scanned tail and the hashed tail compose; NOT covered are annhip_stream_*, annhip_sh_*, annhip_query_slice, query_gpu and
+ * parity mode.  The pair-form calls and the range calls launch the same kernels: a pair is the interval [value, value]. */
 int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int tags_on_device);
 int annhip_index_has_tags(const annhip_index *ix);
 /* Appended rows of fixed mode: the tail (default: none).  A built index is frozen; annhip_index_append adds rows to it
@@ -641,6 +657,32 @@ int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, const ftype *
                                     size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev);
 int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev, ftype *dists_dev,
                        uint32_t *counts_dev, void *hip_stream);
+
+/* ---- range predicates on the tag word: qlo[q] <= (tags[i] & qmask[q]) <= qhi[q] ---------------------------------------- */
+/* The predicate and its identities: "Range predicates on the tag word" in the tag section above.
+ * annhip_query_between: radius_dev == NULL is annhip_query_k(kq) under the range predicate (kq may be the index's own k:
+ * the row is then annhip_query_tagged's where qlo == qhi); radius_dev != NULL is annhip_query_radius with kcap = kq, and
+ * counts_dev is written iff radius_dev != NULL.  ws, hip_stream, outputs and pads as in those calls.  Asynchronous;
+ * returns 0 -- except that with radius_dev == NULL and kq equal to the index's k the call IS annhip_query_tagged's path
+ * and returns what that call returns (0 in fixed mode; kq is the index's own, so annhip_index_max_query_k is not asked).
+ * Returns -2, with one line on stderr, nothing launched and the outputs untouched: while fixed mode is off; on
+ * a resharded index; when any of qmask_dev, qlo_dev, qhi_dev is NULL; on an index without tags; for kq == 0 or
+ * kq > annhip_index_max_query_k(ix); with a radius, for ids_dev == NULL.
+ * annhip_index_exact_query_between: the ground truth, annhip_index_exact_query_k (radius_dev == NULL) or
+ * annhip_index_exact_query_radius (kcap = kq) under the range predicate, over all n_total rows.  Synchronous.  Non-zero
+ * with the outputs untouched: those calls' refusals, and a NULL predicate array.
+ * annhip_exact_knn_between: annhip_exact_knn_tagged with the two bounds apart; its refusals, and a NULL qlo_dev or qhi_dev. */
+long annhip_query_between(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                          size_t kq, const ftype *radius_dev /* NULL: the kq nearest; else annhip_query_radius' rule, kq = kcap */,
+                          const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                          size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev /* written iff radius_dev != NULL */);
+int annhip_index_exact_query_between(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
+                                     const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qlo_dev,
+                                     const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev);
+int annhip_exact_knn_between(size_t n, size_t d, size_t k, const ftype *points_dev, size_t ycnt, const ftype *y_dev, int self,
+                             const uint32_t *tags_dev, const uint32_t *bits_dev /* may be NULL */,
+                             const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                             size_t *ids_dev, ftype *dists_dev);
 
 /* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /

@@ -3,7 +3,7 @@
 (annhip_index_set_filter) and against no filter, on ONE index and the same batches.
 
     python tools/tag_bench.py [--points N] [--dim d] [--knn k] [--tries T] [--queries Q] [--rounds R] [--warmup W]
-                              [--bits 0,8] [--tenants 2,10,100]
+                              [--bits 0,8] [--tenants 2,10,100] [--ranges]
 
 Rows are iid N(0,1), generated on the device (tools/filter_bench.py's data).  For every tenant count S the rows carry a
 tenant field, uniform over S tenants, as their tag word; a tagged batch asks for a random tenant per query (mask
@@ -21,6 +21,12 @@ For every setting:
     (gathered rows + the candidate ids read + per candidate id one tag word and / or one bitmap word + one segment word per
     probed bucket + the query's row, codes, ranked bits, predicate and result keys).
 One JSON line per setting.
+
+--ranges adds the range predicate (annhip_query_between), inside the same alternating rounds and with the same fields; the
+settings above and their lines are what they are without it.  The rows' tag word for these settings is a uniform 16-bit
+value:
+  between_all        (mask, lo, hi) = (0xFFFF, 0, 0xFFFF) for every query: the full interval, the same candidates
+  between_S          for every S of --tenants: a random window per query that holds 1/S of the value space
 """
 import argparse
 import json
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--seed", type=int, default=12345)
     ap.add_argument("--bits", default="0,8")
     ap.add_argument("--tenants", default="2,10,100")
+    ap.add_argument("--ranges", action="store_true", help="add the between_all / between_S settings (annhip_query_between)")
     args = ap.parse_args()
     if args.rounds < 7:
         ap.error("--rounds must be at least 7 (the median is taken over them)")
@@ -69,6 +76,14 @@ def main():
                          torch.randint(0, S, (Q,), device=dev, generator=gen, dtype=torch.int32))
             masks[S] = tags[S] == 0
         zeros = torch.zeros((Q,), dtype=torch.int32, device=dev)
+        if args.ranges:  # (drawn after everything above: the other settings see the data they see without the flag)
+            tags["r16"] = torch.randint(0, 1 << 16, (n,), device=dev, generator=gen, dtype=torch.int32)
+            m16 = torch.full((Q,), 0xFFFF, dtype=torch.int32, device=dev)
+            between = {"all": (m16, zeros, m16)}
+            for S in tenants:
+                width = max(1, (1 << 16) // S)
+                lo = torch.randint(0, (1 << 16) - width + 1, (Q,), device=dev, generator=gen, dtype=torch.int32)
+                between[S] = (m16, lo, lo + (width - 1))
         torch.cuda.synchronize()
     libc.srandom(args.seed)
     ix = A.Index.precomp(points, k, T)
@@ -79,9 +94,13 @@ def main():
         settings.append(("b%d_none" % b, b, None, None, None))
         settings.append(("b%d_bitmap_ones" % b, b, "ones", None, None))
         settings.append(("b%d_tag_all" % b, b, None, tenants[0], (zeros, zeros)))
+        if args.ranges:
+            settings.append(("b%d_between_all" % b, b, None, "r16", between["all"]))
         for S in tenants:
             settings.append(("b%d_tag_%d" % (b, S), b, None, S, wheres[S]))
             settings.append(("b%d_bitmap_%d" % (b, S), b, S, None, None))
+            if args.ranges:
+                settings.append(("b%d_between_%d" % (b, S), b, None, "r16", between[S]))
         settings.append(("b%d_none_again" % b, b, None, None, None))
     ix.set_fixed(True)
     state = {"tags": None}
@@ -130,11 +149,14 @@ def main():
         ids_q = ids_read[b]
         buckets = 1 + ds + b * (b - 1) // 2
         per_id = 4 + (4 if m is not None else 0) + (4 if where is not None else 0)
-        bytes_q = rows_q * d * 4 + ids_q * per_id + T * buckets * 8 + d * 4 + T * 4 + T * b + (8 if where is not None else 0) + (k + 1) * 8
+        bytes_q = rows_q * d * 4 + ids_q * per_id + T * buckets * 8 + d * 4 + T * 4 + T * b + (4 * len(where) if where is not None else 0) + (k + 1) * 8
+        share = tg  # S of the setting: tag_S keeps one tenant of S, between_S a window of 1/S of the 16-bit values
+        if tg == "r16":
+            share = None if name.endswith("_all") else int(name.rsplit("_", 1)[1])
         t = sorted(times[name])
         print(json.dumps({
             "workload": "N=%d d=%d k=%d tries=%d Q=%d float, iid data seed %d, d_short %d" % (n, d, k, T, Q, args.seed, ds),
-            "setting": name, "pair_bits": b, "bitmap": m, "tenants": tg if where is not None else None,
+            "setting": name, "pair_bits": b, "bitmap": m, "tenants": share if where is not None else None,
             "allowed_rows": ix.filter_count, "buckets_per_try": buckets,
             "ms_per_step": round(t[len(t) // 2], 4), "ms_per_step_min_max": [round(t[0], 4), round(t[-1], 4)], "rounds": len(t),
             "stage1_ms": round(s1_ms, 4), "candidate_ids_per_query": round(ids_q, 1),

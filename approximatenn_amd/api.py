@@ -759,6 +759,8 @@ class Index:
             torch.cuda.synchronize()
             self.lib.annhip_index_copy_words(self.h, 1, tg.data_ptr())
             new.set_tags(tg)
+        if self.tag_order is not None:  # the order is carried over by sorting again with the same mask
+            new.sort_tags(self.tag_order[0])
         return new
 
     ROWS = {"native": 0, "f16": 1}  # ANNHIP_ROWS_NATIVE, ANNHIP_ROWS_F16 (include/ann_hip.h)
@@ -823,6 +825,157 @@ class Index:
         """annhip_index_max_query_k: the largest k that query(k=...) accepts on this index (at most 1024)."""
         return int(self.lib.annhip_index_max_query_k(self.h))
 
+    # ---- the tag order (include/ann_hip.h, "the tag order")
+    def sort_tags(self, mask=0xFFFFFFFF):
+        """annhip_index_sort_tags: sort the row ids by (tags & mask, id), so that query_sorted answers a predicate on that
+        mask exactly by scanning only the rows it admits.  mask=0 or None drops the order.  One order and mask per index;
+        8 bytes per row.  set_tags, drop_tail and reshard drop it; set_filter and append keep it (rows appended later are
+        scanned as the tail is).  ValueError for a mask that is no 32-bit word and where the library refuses (no tags, a
+        resharded index); nothing changes then.  Do not call it while batches are in flight."""
+        mask = 0 if mask is None else mask
+        if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or not 0 <= int(mask) <= 0xFFFFFFFF:
+            raise ValueError("sort_tags: mask must be a 32-bit word, got %r" % (mask,))
+        if self.lib.annhip_index_sort_tags(self.h, int(mask)) != 0:
+            raise ValueError("annhip_index_sort_tags refused (no tags, or a resharded index)")
+
+    @property
+    def tag_order(self):
+        """annhip_index_tag_order: (mask, rows) of the current tag order -- rows = n_total at the sort_tags call -- or None."""
+        mask = C.c_uint32()
+        rows = int(self.lib.annhip_index_tag_order(self.h, C.byref(mask)))
+        return (int(mask.value), rows) if rows else None
+
+    def _sorted_pred(self, what, where, Q, device):
+        """where of a sorted call -> (qmask, qlo, qhi) int32 device tensors [Q]; a pair is the interval [value, value].  ValueError
+        without an order and for a mask word other than the order's (free for numpy input, one reduction for device input)."""
+        order = self.tag_order
+        if order is None:
+            raise ValueError("%s: the index has no tag order (Index.sort_tags)" % what)
+        pred = _where_dev(where, Q, device)
+        qm = where[0]
+        if isinstance(qm, np.ndarray):
+            same = bool(np.all(qm == np.uint32(order[0])))
+        else:
+            want = order[0] - (1 << 32) if order[0] >= (1 << 31) else order[0]
+            same = not bool((pred[0] != want).any().item())
+        if not same:
+            raise ValueError("%s: every mask word must equal the order's mask 0x%08X" % (what, order[0]))
+        return (pred[0], pred[1], pred[1]) if len(pred) == 2 else pred
+
+    def tag_runs(self, where):
+        """annhip_tag_runs: per query the run of the tag order its predicate selects -> (start, length), int32 device
+        tensors [Q] (their bits are unsigned): the rows that compete are positions [start, start + length) of the order.
+        where = (qmask, qvalue) or (qmask, qlo, qhi) as in query(); every mask word must equal the order's.  Runs on the
+        current stream.  ValueError without an order, for a wrong mask, shape or dtype."""
+        import torch
+        if not isinstance(where, (tuple, list)) or len(where) not in (2, 3):
+            raise ValueError("where must be a pair (qmask, qvalue) or a triple (qmask, qlo, qhi)")
+        Q = int(where[0].shape[0]) if hasattr(where[0], "shape") and len(where[0].shape) == 1 else -1
+        if Q < 0:
+            raise ValueError("tag_runs: where[0] (qmask) must be a one-dimensional array")
+        dev = where[0].device if isinstance(where[0], torch.Tensor) else torch.device("cuda")
+        return self._runs(*self._sorted_pred("tag_runs", where, Q, dev)[1:])
+
+    def _runs(self, qlo, qhi):
+        """annhip_tag_runs on the current stream for bounds already on the device"""
+        import torch
+        Q, dev = int(qlo.shape[0]), qlo.device
+        start = torch.zeros((Q,), dtype=torch.int32, device=dev)
+        length = torch.zeros((Q,), dtype=torch.int32, device=dev)
+        hold = torch.empty((1,), dtype=torch.int64, device=dev)
+        if self.lib.annhip_tag_runs(self.h, torch.cuda.current_stream(dev).cuda_stream, Q, _ptr(qlo, hold), _ptr(qhi, hold),
+                                    _ptr(start, hold), _ptr(length, hold)) != 0:
+            raise ValueError("annhip_tag_runs refused (no tag order)")
+        return start, length
+
+    def query_sorted(self, y, where, k=None, radius=None, alias=False, ws=None, stream=None):
+        """annhip_query_sorted: the exact answer of a tag predicate by a scan of the rows it admits -> (ids int64 [Q,k],
+        sq dists [Q,k]), or (ids, dists, counts int32 [Q]) with a radius: bit for bit exact_query(y, k=k, where=where) /
+        exact_query_radius, at a cost proportional to the matching rows.  where = (qmask, qvalue) -- the interval
+        [value, value] -- or (qmask, qlo, qhi), every mask word equal to the order's mask (sort_tags).  k=None: the index's
+        k.  The allow list applies, built rows, the tail and rows appended after sort_tags all compete, and the distances
+        are the native rows' whatever set_rows says.  ws and stream as in query(where=).  ValueError without an order, for
+        a wrong mask, a bool or non-integer k, a radius of wrong shape or dtype, and where the library refuses (k outside
+        1..1024 or larger than the rows on offer, a resharded index); nothing is launched then."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        kq = self.k if k is None else self._check_k(k)
+        if kq < 1:
+            raise ValueError("query_sorted: k must be in 1..1024")
+        _, qlo, qhi = self._sorted_pred("query_sorted", where, Q, y.device)
+        rad = _radius_dev(radius, Q, y.dtype, y.device) if radius is not None else None
+        ids = torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device) if rad is not None else None
+        self._sorted(y, alias, kq, rad, qlo, qhi, ids, dists, counts, ws, stream)
+        return (ids, dists) if rad is None else (ids, dists, counts)
+
+    def _sorted(self, y, alias, kq, rad, qlo, qhi, ids, dists, counts, ws, stream):
+        """annhip_query_sorted on `stream` / `ws`: _between's stream and lifetime handling."""
+        import torch
+        if stream is not None and torch.cuda.current_stream(y.device) != stream:
+            stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate (and radius) arrays were made on that one
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        rc = self.lib.annhip_query_sorted(self.h, ws, stream.cuda_stream if stream is not None else None, y.shape[0], _ptr(y, hold),
+                                          int(bool(alias)), kq, _ptr(rad, hold) if rad is not None else None, _ptr(qlo, hold),
+                                          _ptr(qhi, hold), _ptr(ids, hold), _ptr(dists, hold),
+                                          counts.data_ptr() if counts is not None else None)
+        if rc == -2:
+            raise ValueError("annhip_query_sorted refused k=%d (no tag order, k outside 1..1024 or larger than the rows on "
+                             "offer, or a resharded index)" % kq)
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in (qlo, qhi, rad, ids, dists, counts, hold):
+                if t is not None:
+                    t.record_stream(stream)
+        return rc
+
+    def query_routed(self, y, where, scan_below=None, k=None, alias=False, ws=None, stream=None, out_ids=None, out_dists=None):
+        """query(y, where=where, k=k) with a router in front -> (ids int64 [Q,k], sq dists [Q,k], rc).  scan_below=None is
+        that call, nothing else.  With an integer R the queries whose run of the tag order (sort_tags, tag_runs) has at
+        most R rows are answered exactly by query_sorted, the others by the ANN path, and both results are scattered into
+        one output (the host learns the split: one synchronisation).  ValueError without an order, with alias=True (the
+        alias rule names a query by its position in the batch, which a split changes), with a mask other than the order's,
+        and as query(where=) and query_sorted raise it."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        if scan_below is None:
+            return self.query(y, alias=alias, out_ids=out_ids, out_dists=out_dists, ws=ws, stream=stream, where=where, k=k)
+        if isinstance(scan_below, bool) or not isinstance(scan_below, (int, np.integer)) or scan_below < 0:
+            raise ValueError("query_routed: a non-negative integer, got %r" % (scan_below,))
+        if where is None:
+            raise ValueError("query_routed: where must be given")
+        if alias:
+            raise ValueError("query_routed: alias names a query by its position in the batch, which a split changes")
+        Q = y.shape[0]
+        kq = self.k if k is None else self._check_k(k)
+        if kq < 1:
+            raise ValueError("query(k=...): k must be at least 1")
+        qm, qlo, qhi = self._sorted_pred("query_routed", where, Q, y.device)  # an order, and its mask
+        pred = (qm, qlo) + ((qhi,) if len(where) == 3 else ())
+        cur = torch.cuda.current_stream(y.device)
+        run = stream if stream is not None else torch.cuda.default_stream(y.device)  # where the library's launches go
+        if cur != run:
+            run.wait_stream(cur)
+        with torch.cuda.stream(run):
+            _, length = self._runs(qlo, qhi)
+            short = (length.to(torch.int64) & 0xFFFFFFFF) <= int(scan_below)
+            si, li = torch.nonzero(short).reshape(-1), torch.nonzero(~short).reshape(-1)  # (the host learns the split here)
+            ids = out_ids if out_ids is not None else torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+            dists = out_dists if out_dists is not None else torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+            assert tuple(ids.shape) == (Q, kq) and tuple(dists.shape) == (Q, kq)
+            rc = 0
+            if si.numel():
+                i1, d1 = self.query_sorted(y[si].contiguous(), tuple(p[si].contiguous() for p in pred), k=kq, ws=ws, stream=stream)
+                ids[si], dists[si] = i1, d1
+            if li.numel():
+                i2, d2, rc = self.query(y[li].contiguous(), where=tuple(p[li].contiguous() for p in pred), k=k, ws=ws, stream=stream)
+                ids[li], dists[li] = i2, d2
+            if cur != run:
+                for t in (y,) + tuple(pred):
+                    t.record_stream(run)
+        return ids, dists, rc
+
     def query(self, y, alias=False, mode=0, out_ids=None, out_dists=None, ws=None, stream=None, where=None, k=None):
         """annhip_query / annhip_query_on: y torch tensor [Q,d] on the device -> (ids int64 [Q,k], sq dists [Q,k], n_exact).
         ws + stream (a torch.cuda.Stream): run this batch on its own workspace and stream so that it can overlap others.
@@ -836,7 +989,8 @@ class Index:
         as where= is.  ValueError for a bool or a non-integer and where the library refuses (fixed mode off, k out of
         range, where= without tags, a resharded index); nothing is launched then and the outputs are untouched.
         where = (qmask, qlo, qhi), each as above: annhip_query_between -- row i competes for query q iff
-        qlo[q] <= (tags[i] & qmask[q]) <= qhi[q], unsigned; with or without k=, -> (ids, dists, rc); refusals as above."""
+        qlo[q] <= (tags[i] & qmask[q]) <= qhi[q], unsigned; with or without k=, -> (ids, dists, rc); refusals as above.
+        query_routed(y, where, scan_below=R) is this call with the selective queries answered exactly by query_sorted."""
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]

@@ -34,6 +34,7 @@
 #include "ann_tail_hash_kernels.h"
 #include "ann_rerank_kernels.h"
 #include "ann_prune_kernels.h"
+#include "ann_sorted_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -273,9 +274,10 @@ struct EventPair {
 struct annhip_workspace {
   DevBuf codes, cand_d, cand_i, nvt, nvo, top_i, top_d, flist, xids, xd, r2i, r2d, out_i, out_d;
   DevBuf pbits;  // fixed mode with pair bits: u8[Q][T][b] ranked projection indices of this batch (annhip_index_set_probe)
+  DevBuf sorted;  // annhip_query_sorted: u32 start[Q], len[Q], list[Q][3], qmask[Q]
   u32 *d_fcount = NULL;
   void release() {
-    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits};
+    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted};
     for (DevBuf *b : bufs) b->release();
     if (d_fcount) HIPCHECK(hipFree(d_fcount));
     d_fcount = NULL;
@@ -346,6 +348,11 @@ struct annhip_index {
   u32 *tail_codes = NULL;  // [tail_mh][T]
   u32 *tail_off = NULL;    // [T][2^ds + 1], offsets into tail_rows (they include t * tail_mh)
   u32 *tail_rows = NULL;   // [T][tail_mh]
+  // annhip_index_sort_tags (ann_sorted_kernels.h): the row ids [0, ord_ms) ordered by (tags & ord_mask, id) and the masked
+  // words in that order; rows [ord_ms, n_total) are "fresh": appended since, scanned by the tail's kernel
+  u32 *ord_perm = NULL, *ord_keys = NULL;
+  size_t ord_ms = 0;
+  u32 ord_mask = 0;
 };
 static size_t n_total(const annhip_index *ix) { return ix->n + ix->tail_m; }
 static size_t filter_words(size_t rows) { return (rows + 31) / 32; }
@@ -470,9 +477,17 @@ extern "C" void annhip_index_set_fixed(annhip_index *ix, int fixed) {
 }
 // Row tags (annhip_index_set_tags): attributes of the rows, read by annhip_query_tagged and
 // annhip_index_exact_query_tagged only.  Contract: include/ann_hip.h.  Kernels: ann_tag_kernels.h.
+// the tag order goes with the tags it was sorted from (the caller has synchronised)
+static void drop_order(annhip_index *ix) {
+  if (ix->ord_perm) HIPCHECK(hipFree(ix->ord_perm));
+  if (ix->ord_keys) HIPCHECK(hipFree(ix->ord_keys));
+  ix->ord_perm = ix->ord_keys = NULL;
+  ix->ord_ms = 0, ix->ord_mask = 0;
+}
 static void drop_tags(annhip_index *ix) {
   if (ix->tags) HIPCHECK(hipFree(ix->tags));
   ix->tags = NULL;
+  drop_order(ix);
 }
 extern "C" int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int tags_on_device) {
   if (!tags) {
@@ -485,11 +500,52 @@ extern "C" int annhip_index_set_tags(annhip_index *ix, const uint32_t *tags, int
     return -1;
   }
   HIPCHECK(hipDeviceSynchronize());
+  drop_order(ix);  // new tags: the order was sorted from the old ones
   if (!ix->tags) ix->tags = dev_alloc<u32>(ix->n + ix->tail_cap);
   HIPCHECK(hipMemcpy(ix->tags, tags, sizeof(u32) * n_total(ix), tags_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   return 0;
 }
 extern "C" int annhip_index_has_tags(const annhip_index *ix) { return ix->tags ? 1 : 0; }
+// Contract: include/ann_hip.h.  Kernels: ann_sorted_kernels.h.  A stable LSD radix sort of (tags & mask, id), one pass per
+// byte of the mask that has a bit set; synchronous, on the null stream.
+extern "C" int annhip_index_sort_tags(annhip_index *ix, uint32_t field_mask) {
+  if (!field_mask) {
+    if (ix->ord_perm) HIPCHECK(hipDeviceSynchronize());
+    drop_order(ix);
+    return 0;
+  }
+  const char *why = !ix->tags ? "the index has no tags (annhip_index_set_tags)"
+                    : (ix->lo != 0 || ix->hi != ix->n) ? "the index does not hold rows [0, n) on this device (resharded)" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_index_sort_tags: %s\n", why);
+    return -1;
+  }
+  HIPCHECK(hipDeviceSynchronize());
+  drop_order(ix);
+  const size_t ms = n_total(ix);  // (below 2^32 - 16: check_limits and tail_refusal)
+  const u32 nblk = (u32)((ms + ANN_SORT_ITEMS - 1) / ANN_SORT_ITEMS);
+  u32 *keys = dev_alloc<u32>(ms), *perm = dev_alloc<u32>(ms), *keys2 = dev_alloc<u32>(ms), *perm2 = dev_alloc<u32>(ms);
+  u32 *hist = dev_alloc<u32>((size_t)256 * nblk);
+  tsort_init_kernel<<<grid_for(ms, 256, 4096), 256>>>((u32)ms, ix->tags, field_mask, keys, perm);
+  for (int shift = 0; shift < 32 && nblk; shift += 8) {
+    if (!((field_mask >> shift) & 255u)) continue;  // every key has digit 0: the pass would move nothing
+    tsort_count_kernel<<<nblk, 64>>>(keys, (u32)ms, shift, nblk, hist);
+    tsort_scan_kernel<<<1, 1024>>>(hist, (size_t)256 * nblk);
+    tsort_place_kernel<<<nblk, 64>>>(keys, perm, (u32)ms, shift, nblk, hist, keys2, perm2);
+    std::swap(keys, keys2), std::swap(perm, perm2);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipFree(keys2));
+  HIPCHECK(hipFree(perm2));
+  HIPCHECK(hipFree(hist));
+  ix->ord_keys = keys, ix->ord_perm = perm, ix->ord_ms = ms, ix->ord_mask = field_mask;
+  return 0;
+}
+extern "C" size_t annhip_index_tag_order(const annhip_index *ix, uint32_t *field_mask) {
+  if (field_mask) *field_mask = ix->ord_perm ? ix->ord_mask : 0;
+  return ix->ord_perm ? ix->ord_ms : 0;
+}
 // filter_count := the set bits among rows [0, n_total) of the index's bitmap (synchronous, null stream)
 static void filter_recount(annhip_index *ix) {
   const size_t rows = n_total(ix);
@@ -795,6 +851,7 @@ extern "C" int annhip_index_drop_tail(annhip_index *ix) {
   HIPCHECK(hipDeviceSynchronize());
   ix->tail_m = 0;
   drop_tail_hash(ix);
+  drop_order(ix);  // it names tail rows
   if (ix->filter) filter_recount(ix);  // the bitmap and the tags are read up to n again
   return 0;
 }
@@ -2630,7 +2687,10 @@ struct ExShape {
   size_t W, tile_rows, smem, cap;
   bool prefetch;
 };
-static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool prefetch, ExValid valid, ExShape &sh) {
+// sorted: the shape of sorted_scan_kernel (ann_sorted_kernels.h) -- behind the waves' buffers come the tile's ids, its
+// allow-list flags (one word per row each) and the workgroup's (q, start, end) triples; never a prefetch.
+static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool prefetch, ExValid valid, ExShape &sh,
+                        bool sorted = false) {
   const size_t row_bytes = d * sizeof(FT);
   const size_t cap = k + ANN_EX_SLACK;
   size_t np = ANN_EX_GEN_ELEMS / d;
@@ -2641,6 +2701,9 @@ static bool exact_shape(size_t d, size_t k, bool generic, int max_waves, bool pr
     return std::max<size_t>(1, (pf ? (size_t)ANN_EX_PF * 64 * W * 16 : (size_t)ANN_EX_GEN_TILE_BYTES) / row_bytes);
   };
   auto smem_of = [&](size_t W, bool pf) {  // (EX_BITS: the tile's words of the allow list behind the waves' buffers,
+    if (sorted)
+      return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +
+             sizeof(u32) * (2 * tile_rows_of(W, pf) + 3 * W * ANN_EX_QB);
     return ((tile_rows_of(W, pf) * row_bytes + 15) & ~(size_t)15) + W * wave_bytes +  // EX_TAGS: its tag words before them)
            (valid == EX_TAGS ? sizeof(u32) * tile_rows_of(W, pf) : 0) +
            (valid != EX_ALL ? sizeof(u32) * ANN_EX_TBITS(tile_rows_of(W, pf)) : 0);
@@ -3022,6 +3085,103 @@ extern "C" int annhip_index_exact_query_between(annhip_index *ix, size_t ycnt, c
   launch_radius_trim(ycnt, kq, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
                      counts_dev, 0);
   HIPCHECK(hipStreamSynchronize(0));
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- the sorted scan (annhip_query_sorted)
+// Contract: include/ann_hip.h.  Kernels: ann_sorted_kernels.h.  Everything goes to the call's stream; nothing waits.
+static void launch_tag_runs(const annhip_index *ix, size_t Q, const u32 *qlo, const u32 *qhi, u32 *start, u32 *len, hipStream_t s) {
+  if (!Q) return;
+  hipLaunchKernelGGL(tag_runs_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, ix->ord_keys, (u32)ix->ord_ms, (u32)Q, qlo,
+                     qhi, start, len);
+  HIPCHECK(hipGetLastError());
+}
+extern "C" int annhip_tag_runs(annhip_index *ix, void *hip_stream, size_t ycnt, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                               uint32_t *start_dev, uint32_t *len_dev) {
+  if (!ix->ord_perm || !qlo_dev || !qhi_dev || !start_dev || !len_dev || ycnt >= 0xFFFFFFF0ull) return -1;
+  launch_tag_runs(ix, ycnt, qlo_dev, qhi_dev, start_dev, len_dev, (hipStream_t)hip_stream);
+  return 0;
+}
+
+// the scan's launch for this index's row length: false where a row is too long for the LDS of one CU
+static bool launch_sorted_scan(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const u32 *list, size_t *ids, FT *dists,
+                               hipStream_t s, bool dry) {
+  const size_t d = ix->d;
+  const ExValid valid = ix->filter ? EX_BITS : EX_ALL;
+  SortedArgs SA;
+  TailArgs &A = SA.t;
+  A.tail = ix->d_tail, A.y = y, A.in_ids = NULL, A.in_d = NULL, A.out_ids = ids, A.out_d = dists;
+  A.bits = ix->filter, A.tags = NULL, A.qmask = A.qlo = A.qhi = NULL;
+  A.scored = ix->profile == 1 ? ix->d_rows + 8 : NULL;
+  A.n = (u32)ix->n, A.m = (u32)ix->tail_m, A.Q = (u32)Q;
+  A.d = (int)d, A.k = (int)k, A.kin = 0, A.self = alias ? 1 : 0, A.prefetch = 0;
+  SA.points = ix->d_points, SA.perm = ix->ord_perm, SA.list = list;
+  bool ok = true;
+  auto shape = [&](bool generic, int max_waves) {
+    ExShape sh;
+    ok = exact_shape(d, k, generic, max_waves, false, valid, sh, true);
+    A.tile_rows = (int)sh.tile_rows, A.cap = (int)sh.cap;
+    return sh;
+  };
+  const int code = layout_code(d);
+  if (layout_is_generic(code)) {
+    const ExShape sh = shape(true, ANN_EX_GEN_WAVES);
+    if (!ok || dry) return ok;
+    allow_lds(sorted_scan_generic_kernel, sh.smem);
+    hipLaunchKernelGGL(sorted_scan_generic_kernel, dim3((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))),
+                       dim3((unsigned)(64 * sh.W)), sh.smem, s, SA);
+  } else {
+    with_value(QueryLayouts{}, code, [&](auto dc) {
+      constexpr int D = decltype(dc)::value;
+      if constexpr (D != 0 && !OcCode<D>::GEN) {
+        const ExShape sh = shape(false, ExCfg<D>::WAVES);
+        if (!ok || dry) return;
+        const dim3 grid((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))), block((unsigned)(64 * sh.W));
+        auto go = [&](auto kernel) {
+          allow_lds(kernel, sh.smem);
+          hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, SA);
+        };
+        if (valid == EX_BITS) go(sorted_scan_kernel<D, EX_BITS>);
+        else go(sorted_scan_kernel<D, EX_ALL>);
+      }
+    });
+  }
+  if (ok && !dry) HIPCHECK(hipGetLastError());
+  return ok;
+}
+
+extern "C" long annhip_query_sorted(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                                    size_t kq, const ftype *radius_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                                    size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
+  const size_t nt = n_total(ix);
+  const char *why = !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                    : !ix->ord_perm ? "the index has no tag order (annhip_index_sort_tags)"
+                    : !y_dev || !qlo_dev || !qhi_dev || !ids_dev || !dists_dev ? "y_dev, qlo_dev, qhi_dev, ids_dev and dists_dev must all be given"
+                    : kq < 1 || kq > 1024 ? "kq must be in 1..1024"
+                    : kq > nt - (alias && nt ? 1 : 0) ? "kq exceeds the number of rows a query can be given"
+                    : ycnt >= 0xFFFFFFF0ull / 3 ? "query batch too large"
+                    : !launch_sorted_scan(ix, ycnt, NULL, alias, kq, NULL, NULL, NULL, 0, true) ? "row too long for the LDS of one CU" : NULL;
+  if (why) {
+    fprintf(stderr, "annhip_query_sorted: %s\n", why);
+    return -2;
+  }
+  if (!ycnt) return 0;
+  hipStream_t s = (hipStream_t)hip_stream;
+  annhip_workspace &w = ws ? *ws : ix->ws;
+  const FT *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  u32 *start = (u32 *)w.sorted.need(sizeof(u32) * ycnt * 6), *len = start + ycnt, *list = len + ycnt, *qmask = list + 3 * ycnt;
+  launch_tag_runs(ix, ycnt, qlo_dev, qhi_dev, start, len, s);
+  hipLaunchKernelGGL(sorted_order_kernel, dim3((unsigned)((ycnt + 255) / 256)), dim3(256), 0, s, (u32)ycnt, start, len, list);
+  HIPCHECK(hipGetLastError());
+  launch_sorted_scan(ix, ycnt, y, alias, kq, list, ids_dev, dd, s, false);
+  if (nt > ix->ord_ms) {  // the rows appended since the sort: the tail's own scan under the same predicate, merged in place
+    sorted_fill_kernel<<<grid_for(ycnt, 256, 1024), 256, 0, s>>>((u32)ycnt, ix->ord_mask, qmask);
+    HIPCHECK(hipGetLastError());
+    const TagQuery tq{ix->tags, qmask, qlo_dev, qhi_dev};
+    launch_tail_merge(ix, ycnt, y, alias, kq, &tq, kq, ids_dev, dd, ids_dev, dd, NULL, s, ix->ord_ms - ix->n);
+  }
+  if (radius_dev) launch_radius_trim(ycnt, kq, nt, reinterpret_cast<const FT *>(radius_dev), ids_dev, dd, counts_dev, s);
   return 0;
 }
 

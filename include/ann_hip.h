@@ -684,7 +684,50 @@ int annhip_exact_knn_between(size_t n, size_t d, size_t k, const ftype *points_d
                              const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
                              size_t *ids_dev, ftype *dists_dev);
 
-/* ---- synthetic data of the reference's drivers ------------------------------------------------------ */
+/* ---- the tag order: exact answers for selective predicates by sorted scan ----------------------------- */
+/* Where a predicate is selective, do not search the ANN structure: scan exactly the rows that match.  If the row ids are
+ * sorted by tags & field_mask, every pair or range predicate on that mask matches a contiguous run of the sorted order.
+ *
+ * annhip_index_sort_tags: over the ms = n_total rows present at the call, perm[ms] = the row ids ordered by
+ * (tags[id] & field_mask, id) and keys[ms] = the masked words in that order (8 * ms bytes of device memory).  The order is
+ * deterministic: equal masked words are ordered by id.  Synchronous, on the null stream, as annhip_index_set_tags is.
+ * Fixed mode need not be on: tags are row attributes.  field_mask == 0 drops the order.  Returns 0; -1, with one line on
+ * stderr and nothing changed: the index has no tags; the index is resharded.
+ * Drops the order: annhip_index_set_tags (with new tags or with NULL), annhip_index_drop_tail, annhip_index_reshard;
+ * annhip_index_destroy frees the arrays.  Keeps the order: annhip_index_set_filter (the bit is tested at scan time),
+ * annhip_index_append -- rows appended after the call are "fresh": ids in [ms, n_total), scanned by the tail's kernel --,
+ * annhip_index_set_fixed, annhip_index_set_rows, annhip_index_set_probe and annhip_index_hash_tail.
+ * annhip_index_tag_order: the rows the order covers (ms), 0 = none; *field_mask (may be NULL) = its mask, 0 without one.
+ *
+ * annhip_tag_runs: per query the run of the order that its interval selects: start = lower_bound(keys, qlo),
+ * len = upper_bound(keys, qhi) - start; (0, 0) where qlo > qhi.  Asynchronous on hip_stream.  Returns 0; -1 without an
+ * order (or for a NULL array), nothing launched.
+ *
+ * annhip_query_sorted returns what annhip_index_exact_query_between(ix, ycnt, y, alias, kq, radius, M, qlo, qhi, ...)
+ * returns when M[q] = field_mask for every q, bit for bit: per query the kq smallest (distance, id) keys, ascending,
+ * padded with (n_total, +inf), among the rows with qlo[q] <= (tags[i] & field_mask) <= qhi[q] -- built rows and tail rows
+ * both compete, the allow list applies when one is set, row q is left out for query q when aliased.  Distances are the
+ * query path's bits on the NATIVE rows, whatever annhip_index_set_rows says (as annhip_index_exact_query and
+ * annhip_index_rerank).  With a radius, annhip_radius_trim's rule and counts apply; counts_dev is written iff
+ * radius_dev != NULL.  Asynchronous on hip_stream / ws, as annhip_query_between is.  The cost is proportional to the
+ * matching rows: queries whose runs coincide or overlap share the fetch of those rows.
+ * Returns 0.  Returns -2, with one line on stderr, nothing launched and the outputs untouched: without an order; on a
+ * resharded index; for a NULL array (y_dev, qlo_dev, qhi_dev, ids_dev, dists_dev); for kq outside 1..1024 or larger than
+ * n_total - alias; for a row too long for the LDS of one CU.
+ * With annhip_profile(ix, 1), annhip_stats' out[3] additionally counts the rows the scan fetched into tiles (one count
+ * per row and tile fill).
+ * Limits: one order and one mask per index; native rows only; the order is not saved in index files; parity mode,
+ * sharded indexes and annhip_stream_* do not use it; long runs are not split -- one workgroup streams a whole span of
+ * overlapping runs, so a single query whose run is millions of rows runs on one CU: keep such queries on the ANN path. */
+int annhip_index_sort_tags(annhip_index *ix, uint32_t field_mask /* 0: drop the order */);
+size_t annhip_index_tag_order(const annhip_index *ix, uint32_t *field_mask /* may be NULL */);
+int annhip_tag_runs(annhip_index *ix, void *hip_stream, size_t ycnt, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                    uint32_t *start_dev, uint32_t *len_dev);
+long annhip_query_sorted(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                         size_t kq, const ftype *radius_dev /* may be NULL */, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                         size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev /* written iff radius_dev != NULL */);
+
+/* ---- synthetic data of the reference's drivers------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /
  * rand_norm produce (/root/reference/time_results.c:10-13, randNorm.c:9-21), incl. the pending second value of a pair
  * that the reference keeps between calls (annhip_synth_reset() forgets it, as a fresh process would).  Host memory;

@@ -399,6 +399,7 @@ struct OcCode {
   // 128-byte lines: its lines are then touched by two different load instructions, and with non-temporal loads the second
   // touch goes to memory again.  Pure random-row gather, 320-byte rows (d = 80 float, the reference drivers' default):
   // 4.5-4.75 TB/s of row bytes non-temporal, 5.2-5.3 TB/s cached (tools/readbw.hip); 512-byte rows: 6.8 vs 6.3.
+  // (The power-of-two layouts follow the same rule per load instruction: row_loads_nt<D, RT>(), ann_query_kernels.h.)
   static constexpr bool NT_ROWS = OC == 0 || (OC * C * 16) % 128 == 0;
 };
 template <int D>

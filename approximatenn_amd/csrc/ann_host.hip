@@ -275,9 +275,10 @@ struct annhip_workspace {
   DevBuf codes, cand_d, cand_i, nvt, nvo, top_i, top_d, flist, xids, xd, r2i, r2d, out_i, out_d;
   DevBuf pbits;  // fixed mode with pair bits: u8[Q][T][b] ranked projection indices of this batch (annhip_index_set_probe)
   DevBuf sorted;  // annhip_query_sorted: u32 start[Q], len[Q], list[Q][3], qmask[Q]
+  DevBuf tie_d, tie_i;  // pruned stage 1: [Q][k+1] exact candidate lists of the flagged queries (PruneArgs::tie_d / tie_i)
   u32 *d_fcount = NULL;
   void release() {
-    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted};
+    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted, &tie_d, &tie_i};
     for (DevBuf *b : bufs) b->release();
     if (d_fcount) HIPCHECK(hipFree(d_fcount));
     d_fcount = NULL;
@@ -1285,13 +1286,14 @@ static void launch_stage1(annhip_index *ix, const QParams &P, size_t Q, const FT
 // the native rows, certify, apply finalize1's test.  P: the native-row parameters.
 static void launch_prune_rescore(annhip_index *ix, const QParams &P, size_t Q, const FT *y, int kp, const FT *pre_d,
                                  const u32 *pre_i, const u32 *nvt, u32 *nvo, u32 *top_i, FT *top_d, u32 *fl, u32 *d_fcount,
-                                 hipStream_t s) {
+                                 FT *tie_d, u32 *tie_i, hipStream_t s) {
   if (!Q) return;
   if (kp < P.k + 1 || kp > ANN_PRUNE_KMAX || P.k + 1 > 32) die("launch_prune_rescore: preselection size out of range");
   PruneArgs A = {};
   A.points = P.points, A.y = y, A.pre_d = pre_d, A.pre_i = pre_i, A.nv_tot = nvt, A.nv_own = nvo;
   A.top_id = top_i, A.top_dist = top_d, A.flist = fl, A.fcount = d_fcount;
   A.exact_total = ix->d_rows + 2, A.uncertified = ix->d_rows + 4;
+  A.tie_d = tie_d, A.tie_i = tie_i;
   A.E = ix->prune_E;
   A.n = P.n, A.Q = (u32)Q, A.L1 = P.L1, A.P1 = P.P1;
   A.d = P.d, A.k = P.k, A.Kp = kp;
@@ -1522,7 +1524,7 @@ static void launch_exact_select(u32 L, u32 len, u32 in_stride, int k, size_t nq,
   if ((tie.cand_d || tie.derive) && env().tie && L >= 16 && tie.K1 == k + 1 && tie.K1 <= ANN_WAVE && (u32)k <= Pn)
     nw = Pn <= 4096 ? 1 : Pn <= 8192 ? 2 : Pn <= 16384 ? 4 : 0;
   size_t tie_smem = nw ? ann_tie_lds_bytes(nw) : 0;
-  if (nw && !tie.cand_d) tie_smem += ann_tie_derive_bytes(Pn);  // the list derived from the row: its keys live in LDS
+  if (nw && tie.derive) tie_smem += ann_tie_derive_bytes(Pn);  // a list derived from the row: its keys live in LDS
   if (tie_smem > 150 * 1024) nw = 0;
   if (!nw) tie = TieArgs{NULL, NULL, 0, NULL, 0}, tie_smem = 0;
   const size_t smem = std::max(in_lds ? row_smem : (size_t)0, tie_smem);
@@ -1637,13 +1639,13 @@ static long finalize_and_fallback(annhip_index *ix, const QParams &P, size_t Q, 
                                   const u32 *nvt, u32 *top_i, FT *top_d, int ostride, int ooff, DevBuf &flist,
                                   DevBuf &xids, DevBuf &xd, u32 *d_fcount, unsigned long long *rows_done,
                                   unsigned long long *exact_total, bool device_driven, hipStream_t s, size_t qstride = 0,
-                                  bool prefinalized = false) {
-  // prefinalized: stage 1 applied finalize1's test itself (FusedTail.enabled == 2): flist / *d_fcount / top_* are set
-  // cand_d == NULL (with prefinalized; the pruned stage 1, whose uncertified queries have no exact candidate list): the
-  // tie path derives the list from the row, as the staged API does
+                                  bool prefinalized = false, bool lists_may_be_empty = false) {
+  // prefinalized: stage 1 applied finalize1's test itself (FusedTail.enabled == 2, or the pruned stage 1's rescore): flist / *d_fcount / top_* are set
+  // lists_may_be_empty (the pruned stage 1): a flagged query that was not certified has no exact candidate list -- its
+  // list is empty and the tie path derives one from the row, as the staged API does (cand_d == NULL: for every row)
   const int K1 = P.k + 1;
   unsigned long long *tie_ctr = ix ? ix->d_rows + 3 : NULL;
-  const TieArgs tie0 = cand_d ? TieArgs{cand_d, cand_i, K1, tie_ctr, 0} : TieArgs{NULL, NULL, K1, tie_ctr, 1};
+  const TieArgs tie0 = cand_d ? TieArgs{cand_d, cand_i, K1, tie_ctr, lists_may_be_empty ? 1 : 0} : TieArgs{NULL, NULL, K1, tie_ctr, 1};
   u32 nflag = 0;
   u32 *fl = (u32 *)flist.need(sizeof(u32) * Q);
   const size_t row_bytes = (size_t)P.Lc1 * (sizeof(FT) + sizeof(u32));
@@ -1870,6 +1872,12 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
     u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
     u32 *fl = (u32 *)ws.flist.need(sizeof(u32) * Q);
+    // the flagged queries' exact lists for the tie path: buffers of their own (stride K1; pre_d / pre_i have stride kp and
+    // are still being read by other waves of the rescore kernel)
+#ifndef ANN_PRUNE_NO_TIE_LIST  // (A/B builds: no lists, every flagged row derives its own as before)
+    cand_d = (FT *)ws.tie_d.need(sizeof(FT) * Q * K1);
+    cand_i = (u32 *)ws.tie_i.need(sizeof(u32) * Q * K1);
+#endif
     prefinalized = true;
     if (!fcount_zeroed) zero_u32_kernel<<<1, 1, 0, s>>>(ws.d_fcount);
     QParams Pn = P;
@@ -1879,9 +1887,9 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     if (ix->profile) ev = s1_prof_begin(ix, s);
     launch_stage1(ix, Pn, Q, y, alias, codes, pre_d, pre_i, nvt, nvo, s, ix->h_tries, ix->use_seg,
                   FusedTail{0, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL}, NULL, 1, env().s1_slots, qstride, kp, false);
-    launch_prune_rescore(ix, P, Q, y, kp, pre_d, pre_i, nvt, nvo, top_i, top_d, fl, ws.d_fcount, s);
+    launch_prune_rescore(ix, P, Q, y, kp, pre_d, pre_i, nvt, nvo, top_i, top_d, fl, ws.d_fcount, cand_d, cand_i, s);
     if (ix->profile) s1_prof_end(ix, ev, Q, nvo, s);
-    // cand_d / cand_i stay NULL: the exact path of a flagged query derives its own list
+    // cand_d / cand_i: a certified flagged query's exact list; an uncertified one's is empty and the tie path derives it
   } else
 #endif
   if (mode == 0) {
@@ -1901,7 +1909,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
   unsigned long long *rows_ctr = ix->profile == 1 ? ix->d_rows + 8 : NULL;
   long nflag = finalize_and_fallback(ix, P, Q, y, alias, codes, mode, cand_d, cand_i, nvt, top_i, top_d, k, 0,
                                      ws.flist, ws.xids, ws.xd, ws.d_fcount, rows_ctr, ix->d_rows + 2, true, s, qstride,
-                                     prefinalized);
+                                     prefinalized, pruned);
   seg_mark(ix, marks, s);
   // stage 2 (det_results second half, alg.c:314-327)
   FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * k);

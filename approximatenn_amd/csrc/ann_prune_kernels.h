@@ -33,36 +33,30 @@ struct PruneArgs {
   FT *top_dist;
   u32 *flist, *fcount;
   unsigned long long *exact_total, *uncertified;
+  FT *tie_d;          // [Q][k+1] a flagged query's exact candidate list for the tie path (ann_tie.h): certified = the
+  u32 *tie_i;         // min(m, k+1) smallest exact keys ascending, (+inf, ANN_ID_NONE) pads; uncertified = empty.  Or NULL
   double E;
   u32 n, Q, L1, P1;
   int d, k, Kp;
 };
 
+// The second half for ONE query on ONE wave, wherever the caller has the preselection.  a: the query row as this lane's
+// slice (ExLanes<D>: the gathers' lane map); myid: this lane's preselected id (lanes >= Kp and pads: ANN_ID_NONE); B: the
+// Kp-th preselect distance (+inf where fewer were found); vtot / vown: the query's valid slots / narrow rows gathered;
+// keys, sorted, ids: this wave's LDS scratch, Kp entries each.  (Called from wave 0 of the stage-1 workgroup on its
+// kout it costs that kernel a wave per SIMD: profiles/prune_tail_devcode.md.)
 template <int D>
-__global__ __launch_bounds__(64 * ANN_PRUNE_WAVES) void prune_rescore_kernel(PruneArgs A) {
-  __shared__ Key s_keys[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX], s_sorted[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX];
-  __shared__ u32 s_ids[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX];
+__device__ __forceinline__ void prune_rescore_wave(const PruneArgs &A, u32 q, const VT (&a)[RowChunks<D>::C], u32 myid, FT B,
+                                                   u32 vtot, u32 vown, Key *keys, Key *sorted, u32 *ids) {
   constexpr int C = RowChunks<D>::C;
-  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int lane = lane_id();
   const int d = A.d, k = A.k, K1 = A.k + 1, Kp = A.Kp;
-  const u32 q = __builtin_amdgcn_readfirstlane(blockIdx.x * ANN_PRUNE_WAVES + w);
-  if (q >= A.Q) return;  // no workgroup barrier below
-  Key *keys = s_keys[w], *sorted = s_sorted[w];
-  u32 *ids = s_ids[w];
   // the preselected ids (distinct: stage 1 selects distinct keys and an id has one distance)
-  const u32 myid = lane < Kp ? A.pre_i[(size_t)q * Kp + lane] : ANN_ID_NONE;
   const bool real = myid < A.n;
   const u64 rm = __ballot(real);
   const int m = __builtin_popcountll(rm);
   if (real) ids[mask_rank(rm)] = myid;
   const ExLanes<D> ln(d, lane);
-  VT a[C];
-  const FT *yq = A.y + (size_t)q * d;
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    if constexpr (D > 0) a[c] = reinterpret_cast<const VT *>(yq)[ln.p + c * ln.oc];
-    else a[c] = oc_load_chunk<D, false>(yq, ln.p + c * ln.oc, d);
-  }
   wave_lds_sync();
   const FT *__restrict__ points = A.points;
   auto load = [&](VT(&b)[C], int r0, u32 &id) {
@@ -104,11 +98,11 @@ __global__ __launch_bounds__(64 * ANN_PRUNE_WAVES) void prune_rescore_kernel(Pru
   // ---- certificate
   bool cert = m < Kp;
   if (!cert && m >= K1) {
-    const double B = (double)A.pre_d[(size_t)q * Kp + Kp - 1];
+    const double Bd = (double)B;
     const double tau = (double)key_dist(sorted[K1 - 1]);
     const double g1 = 1.0 - 0x1p-16;
-    const double r = sqrt(B * g1) - A.E;
-    if (B >= 0x1p-100 && r > 0.0) {
+    const double r = sqrt(Bd * g1) - A.E;
+    if (Bd >= 0x1p-100 && r > 0.0) {
       const double LB = (r * r) * g1 * (1.0 - 0x1p-40);  // the last factor: the roundings of this expression itself
       if (LB > tau) cert = true;
     }
@@ -118,12 +112,20 @@ __global__ __launch_bounds__(64 * ANN_PRUNE_WAVES) void prune_rescore_kernel(Pru
   for (int t = lane; t + 1 < me_cnt; t += ANN_WAVE)
     if (ft_bits(key_dist(sorted[t])) == ft_bits(key_dist(sorted[t + 1]))) bad = true;
   if (me_cnt >= k && !(key_dist(sorted[k - 1]) < ft_inf())) bad = true;
-  if (A.L1 > A.P1 && A.nv_tot[q] >= A.P1) bad = true;
+  if (A.L1 > A.P1 && vtot >= A.P1) bad = true;
   if (!cert || __ballot(bad) != 0) {
     if (lane == 0) {
       A.flist[atomicAdd(A.fcount, 1u)] = q;
       if (A.exact_total) atomicAdd(A.exact_total, 1ull);
       if (!cert && A.uncertified) atomicAdd(A.uncertified, 1ull);
+    }
+    // The flagged query's candidate list for the exact step's tie path.  Certified: sorted[0 .. me_cnt) are the smallest
+    // keys of the WHOLE candidate row (every key left out lies strictly above the K1-th), i.e. the list native stage 1
+    // writes for a rejected query.  Uncertified: nothing is known about the row, the list is empty.
+    if (A.tie_d && lane < K1) {
+      const bool have = cert && lane < me_cnt;
+      A.tie_d[(size_t)q * K1 + lane] = have ? key_dist(sorted[lane]) : ft_inf();
+      A.tie_i[(size_t)q * K1 + lane] = have ? key_id(sorted[lane]) : ANN_ID_NONE;
     }
   } else {
     for (int t = lane; t < k; t += ANN_WAVE) {
@@ -131,7 +133,27 @@ __global__ __launch_bounds__(64 * ANN_PRUNE_WAVES) void prune_rescore_kernel(Pru
       A.top_dist[(size_t)q * k + t] = key_dist(sorted[t]);
     }
   }
-  if (lane == 0 && A.nv_own) A.nv_own[q] = (A.nv_own[q] + 1) / 2 + (u32)m;
+  if (lane == 0 && A.nv_own) A.nv_own[q] = (vown + 1) / 2 + (u32)m;
+}
+
+template <int D>
+__global__ __launch_bounds__(64 * ANN_PRUNE_WAVES) void prune_rescore_kernel(PruneArgs A) {
+  __shared__ Key s_keys[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX], s_sorted[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX];
+  __shared__ u32 s_ids[ANN_PRUNE_WAVES][ANN_PRUNE_KMAX];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const u32 q = __builtin_amdgcn_readfirstlane(blockIdx.x * ANN_PRUNE_WAVES + w);
+  if (q >= A.Q) return;  // no workgroup barrier below
+  const ExLanes<D> ln(A.d, lane);
+  VT a[RowChunks<D>::C];
+  const FT *yq = A.y + (size_t)q * A.d;
+#pragma unroll
+  for (int c = 0; c < RowChunks<D>::C; c++) {
+    if constexpr (D > 0) a[c] = reinterpret_cast<const VT *>(yq)[ln.p + c * ln.oc];
+    else a[c] = oc_load_chunk<D, false>(yq, ln.p + c * ln.oc, A.d);
+  }
+  const u32 myid = lane < A.Kp ? A.pre_i[(size_t)q * A.Kp + lane] : ANN_ID_NONE;
+  prune_rescore_wave<D>(A, q, a, myid, A.pre_d[(size_t)q * A.Kp + A.Kp - 1], A.nv_tot[q], A.nv_own ? A.nv_own[q] : 0u, s_keys[w],
+                        s_sorted[w], s_ids[w]);
 }
 
 // out[0] = max over the rows of ||p - h(p)||^2 as the bits of a non-negative double (they order like the values);

@@ -105,6 +105,32 @@ __device__ __forceinline__ typename RowRaw<RT>::T load_row_raw(const RT *row, in
     else return *p;
   }
 }
+// The load policy of a gathered row in the power-of-two layouts: non-temporal exactly when ONE load instruction of a
+// row's lane group (LPR lanes x one raw chunk) covers whole 128-byte lines.  A piece of a line comes back with the
+// next instruction, and a non-temporal first touch has not kept it: the second touch goes out to memory again (the
+// ceiling run with the narrow rows' lane map, random 256-byte rows as 4 x 8 bytes per lane at 16 / 24 / 32 waves per
+// CU: non-temporal 5.57 / 5.05 / 5.53 TB/s, cached 6.18 / 6.07 / 5.80).  OcCode<D>::NT_ROWS is the same rule for
+// the oc layouts.  -DANN_S1_NARROW_NT=0/1 overrides it for the narrow rows (A/B builds).
+template <int D, typename RT>
+constexpr bool row_loads_nt() {
+#ifdef ANN_S1_NARROW_NT
+  if (!std::is_same<RT, FT>::value) return ANN_S1_NARROW_NT != 0;
+#endif
+  return (RowLay<D>::LPR * (int)sizeof(typename RowRaw<RT>::T)) % 128 == 0;
+}
+#ifndef ANN_S1_NARROW_NT
+#ifdef USE_FLOAT
+static_assert(row_loads_nt<128, FT>() && !row_loads_nt<128, RN>(), "d = 128: native rows by whole lines, binary16 rows by halves");
+static_assert(row_loads_nt<64, FT>() && !row_loads_nt<64, RN>() && row_loads_nt<32, FT>() && !row_loads_nt<32, RN>(),
+              "d = 32, 64: 8 lanes per row, 128 bytes of a native row and 64 of a binary16 one per instruction");
+static_assert(row_loads_nt<256, FT>() && row_loads_nt<256, RN>(), "d = 256: 16 lanes per row, whole lines either way");
+#else
+static_assert(row_loads_nt<128, FT>() && row_loads_nt<128, RN>() && row_loads_nt<256, FT>() && row_loads_nt<256, RN>(),
+              "f64 library, d = 128, 256: 16 / 32 lanes per row, whole lines of native and of binary32 rows");
+static_assert(row_loads_nt<64, FT>() && !row_loads_nt<64, RN>() && row_loads_nt<32, FT>() && !row_loads_nt<32, RN>(),
+              "f64 library, d = 32, 64: 8 lanes per row, 128 bytes of a native row and 64 of a binary32 one per instruction");
+#endif
+#endif
 
 // Chunk `ci` of a row of d elements in the layouts D < 0.  Aligned layouts: one 16-byte load (NT as above; 8 bytes for a
 // narrow row); the unaligned one: element by element, zeros beyond d (never read by the tree, which starts at d).
@@ -642,7 +668,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
         idb[s] = list[first + g < cnt ? first + g : first];
         const RT *rp = rows + (size_t)(idb[s] - P.lo) * D;
 #pragma unroll
-        for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
+        for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, row_loads_nt<D, RT>()>(rp, p + c * L::LPR);
       }
     }
     for (int base = 0; base < cnt; base += PF * L::RPW) {
@@ -658,7 +684,7 @@ __device__ __forceinline__ void gather_select(const QParams &P, const u32 *list,
             idb[s] = list[nb + g < cnt ? nb + g : nb];
             const RT *rp = rows + (size_t)(idb[s] - P.lo) * D;
 #pragma unroll
-            for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
+            for (int c = 0; c < L::C; c++) buf[s][c] = load_row_raw<RT, row_loads_nt<D, RT>()>(rp, p + c * L::LPR);
           }
           const Key key = key_make(dist, id);
           const bool pass = act && p == 0 && key_less(key, S.tau);
@@ -777,7 +803,7 @@ __device__ __forceinline__ u32 stage2_in_workgroup(const QParams &P, u32 x, int 
           const u32 id = t_gid[r < cnt2 ? r : base0];
           const RT *rp = rows + (size_t)(id - P.lo) * D;
 #pragma unroll
-          for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
+          for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, row_loads_nt<D, RT>()>(rp, p + c * L::LPR);
         }
       }
 #pragma unroll
@@ -1698,7 +1724,7 @@ __global__ __launch_bounds__(256) void row_dists_kernel(QParams P, int Q, const 
             const u32 id = lid[r < cnt ? r : base0];
             const RT *rp = rows + (size_t)(id - P.lo) * D;
 #pragma unroll
-            for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, true>(rp, p + c * L::LPR);
+            for (int c = 0; c < L::C; c++) b[u][c] = load_row_raw<RT, row_loads_nt<D, RT>()>(rp, p + c * L::LPR);
           }
         }
 #pragma unroll
@@ -1824,7 +1850,8 @@ struct TieArgs {
   const u32 *cand_i;
   int K1;
   unsigned long long *resolved;  // statistics: rows answered by the tie path
-  int derive;         // cand_d == NULL: derive the list from the row itself (tie_derive_list)
+  int derive;         // derive the list from the row itself (tie_derive_list): every row's where cand_d == NULL, else the
+                      // rows' whose list is empty (first id ANN_ID_NONE: a query the pruned stage 1 could not certify)
 };
 template <bool USE_LDS, int NW>
 __global__ __launch_bounds__(1024) void exact_select_kernel(u32 L, u32 len, u32 in_stride, int k,
@@ -1846,12 +1873,16 @@ __global__ __launch_bounds__(1024) void exact_select_kernel(u32 L, u32 len, u32 
       const size_t o = (size_t)x * ostride + ooff;
       const FT *cd = T.cand_d ? T.cand_d + (size_t)x * T.K1 : NULL;
       const u32 *ci = T.cand_d ? T.cand_i + (size_t)x * T.K1 : NULL;
-      if (!T.cand_d && L >= 16 && T.K1 <= ANN_WAVE) {
+      const bool empty = !T.cand_d || (T.derive && ci[0] == ANN_ID_NONE);  // workgroup-uniform
+      if (empty) cd = NULL;
+      if (empty && T.derive && L >= 16 && T.K1 <= ANN_WAVE) {
         FT *dcd;
         u32 *dci;
         tie_derive_list((u32)1 << ann_lg(L), T.K1, gi, gd, smem + ann_tie_lds_bytes(NW), &dcd, &dci);
         cd = dcd, ci = dci;
       }
+      // A list written by the pruned stage 1's rescore is the list native stage 1 writes: the certificate's LB > tau is
+      // strict, so every key the preselection left out lies strictly above the K1-th exact key.
       const bool done = cd && tie_resolve<NW>(L, k, T.K1, gi, gd, cd, ci, smem,
                                               out64 ? NULL : out_id + o, out64 ? out64 + o : NULL, out_dist + o, T.resolved);
       if (done) {

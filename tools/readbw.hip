@@ -5,7 +5,9 @@
 //     ~14M rows like one cfg3 launch.  Measured round 1: stream 6.2 TB/s cached / 6.95 TB/s nt; gather 6.3 / 6.8 TB/s.
 // (3) random 320-byte rows (d = 80 float, static 5-lane layout);
 // (4) random 256-byte rows (d = 128 in binary16, annhip_index_set_rows): 8 lanes x 4 x 8 B per row -- the load form of the
-//     binary16 stage-1 kernel (same lane map as the float rows, chunks of 4 halves) -- and 8 lanes x 2 x 16 B per row.
+//     binary16 stage-1 kernel (same lane map as the float rows, chunks of 4 halves) -- and 8 lanes x 2 x 16 B per row;
+// (5) random 1-KB rows (d = 256 in binary32, the f64 library's narrow rows): 32 lanes x 4 x 8 B per row, 2 rows per wave
+//     pass -- one load instruction covers two whole lines of the row.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,10 +64,11 @@ __global__ __launch_bounds__(256) void gather320(const v4 *p, size_t nrows, size
   }
   if (acc.x + acc.y + acc.z + acc.w == 12345.678f) out[0] = 1;
 }
-// random 256-byte rows, 8 lanes per row, C chunks of sizeof(V) bytes each: lane q takes chunks q, q+8, ... (the stage-1 map)
-template <typename V, int C, bool NT>
+// random rows of LPR * C * sizeof(V) bytes (256 with 8 lanes per row), LPR lanes per row, C chunks of sizeof(V) bytes each:
+// lane q takes chunks q, q+LPR, ... (the stage-1 map)
+template <typename V, int C, bool NT, int LPR = 8>
 __global__ __launch_bounds__(256) void gather256(const V *p, size_t nrows, size_t per_wave, float *out) {
-  const int lane = threadIdx.x & 63, g = lane >> 3, q = lane & 7;
+  const int lane = threadIdx.x & 63, g = lane / LPR, q = lane % LPR;
   size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   V acc = {};
   unsigned long long h = wave * 0x9E3779B97F4A7C15ull + 12345;
@@ -74,9 +77,9 @@ __global__ __launch_bounds__(256) void gather256(const V *p, size_t nrows, size_
     unsigned long long hh = h + g * 0xD1B54A32D192ED03ull;
     hh ^= hh >> 29; hh *= 0xBF58476D1CE4E5B9ull; hh ^= hh >> 32;
     size_t row = hh % nrows;
-    const V *rp = p + row * (8 * C) + q;
+    const V *rp = p + row * (LPR * C) + q;
 #pragma unroll
-    for (int c = 0; c < C; c++) acc += NT ? __builtin_nontemporal_load(rp + c * 8) : rp[c * 8];
+    for (int c = 0; c < C; c++) acc += NT ? __builtin_nontemporal_load(rp + c * LPR) : rp[c * LPR];
   }
   if (acc[0] + acc[1] == 12345.678f) out[0] = 1;
 }
@@ -126,6 +129,18 @@ int main() {
     time([&] { gather256<v2, 4, false><<<blocks, 256>>>(reinterpret_cast<const v2 *>(p), nrows256, per_wave, out); }, nm, gb);
     snprintf(nm, 96, "random 256B rows 2x16B nt  %2d waves/CU", wpc);
     time([&] { gather256<v4, 2, true><<<blocks, 256>>>(p, nrows256, per_wave, out); }, nm, gb);
+    snprintf(nm, 96, "random 256B rows 2x16B cached %2d waves/CU", wpc);
+    time([&] { gather256<v4, 2, false><<<blocks, 256>>>(p, nrows256, per_wave, out); }, nm, gb);
+  }
+  size_t nrows1k = bytes / 1024;
+  for (int wpc : {8, 16, 24, 32}) {
+    int blocks = 256 * wpc / 4; size_t waves = (size_t)blocks * 4, per_wave = 7000000 / 2 / waves + 1;
+    double gb = (double)waves * per_wave * 2 * 1024 / 1e6;
+    char nm[96];
+    snprintf(nm, 96, "random 1KB rows 32x4x8B nt  %2d waves/CU", wpc);
+    time([&] { gather256<v2, 4, true, 32><<<blocks, 256>>>(reinterpret_cast<const v2 *>(p), nrows1k, per_wave, out); }, nm, gb);
+    snprintf(nm, 96, "random 1KB rows 32x4x8B cached %2d waves/CU", wpc);
+    time([&] { gather256<v2, 4, false, 32><<<blocks, 256>>>(reinterpret_cast<const v2 *>(p), nrows1k, per_wave, out); }, nm, gb);
   }
   return 0;
 }

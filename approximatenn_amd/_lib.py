@@ -129,6 +129,10 @@ def load(prec="f32"):
     lib.annhip_tag_runs.argtypes = [vp, vp, sz, vp, vp, vp, vp]
     lib.annhip_query_sorted.restype = C.c_long
     lib.annhip_query_sorted.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, vp, vp]
+    lib.annhip_tag_runs_set.restype = C.c_int
+    lib.annhip_tag_runs_set.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.annhip_query_sorted_set.restype = C.c_long
+    lib.annhip_query_sorted_set.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.annhip_radius_trim.restype = C.c_int
     lib.annhip_radius_trim.argtypes = [sz, sz, sz, vp, vp, vp, vp, vp]
     lib.annhip_rerank.restype = C.c_int
@@ -258,6 +262,7 @@ EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp
             "annhip_query_radius", "annhip_index_exact_query_radius", "annhip_radius_trim",
             "annhip_query_between", "annhip_index_exact_query_between", "annhip_exact_knn_between",
             "annhip_index_sort_tags", "annhip_index_tag_order", "annhip_tag_runs", "annhip_query_sorted",
+            "annhip_tag_runs_set", "annhip_query_sorted_set",
             "annhip_rerank", "annhip_index_rerank",
             "annhip_index_append", "annhip_index_reserve_tail", "annhip_index_tail", "annhip_index_copy_rows", "annhip_index_drop_tail",
             "annhip_index_hash_tail", "annhip_index_tail_hashed",

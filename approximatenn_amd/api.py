@@ -276,6 +276,85 @@ def _where_dev(where, Q, device):
             _words_dev(where[2], Q, device, "where[2] (qhi)"))
 
 
+def where_in(mask, sets):
+    """The CSR form of per-query sets of values or intervals for Index.query_sorted_set / tag_runs_set -> (mask, off, lo, hi):
+    sets[q] is a list whose items are values v -- the interval [v, v] -- or pairs (lo, hi), all 32-bit words; off is numpy
+    int64 [Q + 1], lo and hi numpy uint32 [off[-1]].  ValueError for a mask or an item that is no 32-bit word, for an item
+    of another shape and for a set of more than 256 items."""
+    def word(x, what):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) <= 0xFFFFFFFF:
+            raise ValueError("where_in: %s must be a 32-bit word, got %r" % (what, x))
+        return int(x)
+    mask = word(mask, "mask")
+    off, lo, hi = [0], [], []
+    for q, items in enumerate(sets):
+        items = list(items)
+        if len(items) > 256:
+            raise ValueError("where_in: query %d has %d intervals, at most 256 are allowed" % (q, len(items)))
+        for it in items:
+            if isinstance(it, (tuple, list)):
+                if len(it) != 2:
+                    raise ValueError("where_in: an item is a value or a pair (lo, hi), got %r" % (it,))
+                lo.append(word(it[0], "lo")), hi.append(word(it[1], "hi"))
+            else:
+                v = word(it, "a value")
+                lo.append(v), hi.append(v)
+        off.append(len(lo))
+    return mask, np.asarray(off, dtype=np.int64), np.asarray(lo, dtype=np.uint32), np.asarray(hi, dtype=np.uint32)
+
+
+def _check_off(off):
+    """the offsets of a CSR set form -> numpy uint32 [Q + 1]; ValueError unless they are an integer array that starts at 0,
+    does not decrease and gives no query more than 256 intervals"""
+    if not isinstance(off, np.ndarray) or off.ndim != 1 or off.shape[0] < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("off must be a one-dimensional numpy integer array [Q + 1]")
+    o = off.astype(np.int64)
+    if o[0] != 0 or (np.diff(o) < 0).any() or o[-1] > 0xFFFFFFFF:
+        raise ValueError("off must start at 0 and must not decrease")
+    if o.shape[0] > 1 and int(np.diff(o).max()) > 256:
+        raise ValueError("a query has more than 256 intervals")
+    return np.ascontiguousarray(o.astype(np.uint32))
+
+
+def normalize_intervals(off, lo, hi):
+    """The normalisation that annhip_query_sorted_set applies to its sets, in numpy -> (lo, hi) uint32 of the same length:
+    within each query's slice the intervals are ordered by (lo, hi); empty ones (lo > hi) and those that an earlier one
+    covers become (1, 0); each other one is clipped to start above the largest hi before it.  The non-empty results of a
+    query are pairwise disjoint and their union is the union of the input."""
+    o = _check_off(off).astype(np.int64)
+    lo, hi = np.asarray(lo, dtype=np.uint32), np.asarray(hi, dtype=np.uint32)
+    if lo.shape != (int(o[-1]),) or hi.shape != lo.shape:
+        raise ValueError("lo and hi must have length off[-1]")
+    nlo, nhi = np.empty_like(lo), np.empty_like(hi)
+    for q in range(o.shape[0] - 1):
+        a, b = int(o[q]), int(o[q + 1])
+        order = np.lexsort((hi[a:b], lo[a:b]))
+        top = -1  # the largest hi so far
+        for j, i in enumerate(order):
+            l, h = int(lo[a + i]), int(hi[a + i])
+            if l > h or h <= top:
+                l, h = 1, 0
+            else:
+                l, top = max(l, top + 1), h
+            nlo[a + j], nhi[a + j] = l, h
+    return nlo, nhi
+
+
+def set_pieces(start, length, split):
+    """The list entries that annhip_query_sorted_set makes of runs (start, length) -> (slot, piece start, piece end) int64
+    arrays: split=0 one entry per run, empty ones included; split=S > 0 every non-empty run cut at the global multiples of
+    S.  The host-side model of the staging."""
+    start, length = np.asarray(start).astype(np.int64) & 0xFFFFFFFF, np.asarray(length).astype(np.int64) & 0xFFFFFFFF
+    slot, ps, pe = [], [], []
+    for j, (s, n) in enumerate(zip(start.tolist(), length.tolist())):
+        if not split:
+            slot.append(j), ps.append(s), pe.append(s + n)
+        elif n:
+            for t in range(s // split, (s + n - 1) // split + 1):
+                slot.append(j), ps.append(max(s, t * split)), pe.append(min(s + n, (t + 1) * split))
+    return np.asarray(slot, dtype=np.int64), np.asarray(ps, dtype=np.int64), np.asarray(pe, dtype=np.int64)
+
+
 def order_key(values):
     """The order-preserving map of a numeric column into tag words -> numpy uint32 of the same shape: a <= b iff
     order_key(a) <= order_key(b) as unsigned words, so the result serves as, or inside, a tag word and as the bounds of
@@ -929,6 +1008,84 @@ class Index:
                 if t is not None:
                     t.record_stream(stream)
         return rc
+
+    def _set_pred(self, what, where, device):
+        """where = (mask, off, lo, hi) of a set call -> (off uint32 numpy [Q + 1], lo, hi int32 device tensors [off[-1]]);
+        ValueError without an order, for a mask other than the order's and for malformed arrays"""
+        order = self.tag_order
+        if order is None:
+            raise ValueError("%s: the index has no tag order (Index.sort_tags)" % what)
+        if not isinstance(where, (tuple, list)) or len(where) != 4:
+            raise ValueError("%s: where must be (mask, off, lo, hi)" % what)
+        mask, off, lo, hi = where
+        if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or int(mask) != order[0]:
+            raise ValueError("%s: the mask must equal the order's mask 0x%08X" % (what, order[0]))
+        off = _check_off(off)
+        T = int(off[-1])
+        return off, _words_dev(lo, T, device, "where[2] (lo)"), _words_dev(hi, T, device, "where[3] (hi)")
+
+    def tag_runs_set(self, where):
+        """annhip_tag_runs_set: the runs of the normalised intervals of every query's set -> (start, length), int32 device
+        tensors [off[-1]] (their bits are unsigned), in the order of normalize_intervals; (0, 0) for the slots it
+        emptied.  where = (mask, off, lo, hi) as where_in builds it.  Runs on the current stream and stages its offsets
+        in the index's own workspace.  ValueError without an order, for a wrong mask and for malformed arrays."""
+        import torch
+        dev = where[2].device if isinstance(where, (tuple, list)) and len(where) == 4 and isinstance(where[2], torch.Tensor) \
+            else torch.device("cuda")
+        off, lo, hi = self._set_pred("tag_runs_set", where, dev)
+        T = int(off[-1])
+        start = torch.zeros((T,), dtype=torch.int32, device=dev)
+        length = torch.zeros((T,), dtype=torch.int32, device=dev)
+        hold = torch.empty((1,), dtype=torch.int64, device=dev)
+        if self.lib.annhip_tag_runs_set(self.h, torch.cuda.current_stream(dev).cuda_stream, off.shape[0] - 1, off.ctypes.data,
+                                        _ptr(lo, hold), _ptr(hi, hold), _ptr(start, hold), _ptr(length, hold)) != 0:
+            raise ValueError("annhip_tag_runs_set refused")
+        return start, length
+
+    def query_sorted_set(self, y, where, k=None, radius=None, split=0, alias=False, ws=None, stream=None):
+        """annhip_query_sorted_set: query_sorted for a union of intervals per query -> (ids int64 [Q,k], sq dists [Q,k],
+        entries), or (ids, dists, counts int32 [Q], entries) with a radius.  where = (mask, off, lo, hi): mask the
+        order's, off a numpy integer array [Q + 1], lo / hi numpy uint32 arrays or int32 device tensors [off[-1]]
+        (where_in builds them); row i competes for query q iff lo[j] <= (tags[i] & mask) <= hi[j] for some j in
+        [off[q], off[q + 1]).  split=S > 0 cuts every run at the global multiples of S rows of the order, so that a long
+        run is scanned by many workgroups; the call then waits once for its stream to learn the piece count.  split=0
+        cuts nothing and waits for nothing.  entries = the non-empty runs (split=0: a device scalar, reading it
+        synchronises) or the pieces (split > 0: an int).  Everything else is query_sorted's.  ValueError where that raises
+        it, for malformed sets, more than 256 intervals in one, 0 < split < 64 and more than 2^27 entries x k; nothing of
+        the scan is launched then."""
+        import torch
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        Q = y.shape[0]
+        kq = self.k if k is None else self._check_k(k)
+        if kq < 1:
+            raise ValueError("query_sorted_set: k must be in 1..1024")
+        if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not (split == 0 or 64 <= split <= 0xFFFFFFFF):
+            raise ValueError("query_sorted_set: split must be 0 or an integer in 64..2^32-1, got %r" % (split,))
+        off, lo, hi = self._set_pred("query_sorted_set", where, y.device)
+        if off.shape[0] != Q + 1:
+            raise ValueError("query_sorted_set: off must have length Q + 1 = %d" % (Q + 1))
+        rad = _radius_dev(radius, Q, y.dtype, y.device) if radius is not None else None
+        ids = torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device) if rad is not None else None
+        if stream is not None and torch.cuda.current_stream(y.device) != stream:
+            stream.wait_stream(torch.cuda.current_stream(y.device))
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        rc = self.lib.annhip_query_sorted_set(self.h, ws, stream.cuda_stream if stream is not None else None, Q, _ptr(y, hold),
+                                              int(bool(alias)), kq, _ptr(rad, hold) if rad is not None else None, off.ctypes.data,
+                                              _ptr(lo, hold), _ptr(hi, hold), int(split), _ptr(ids, hold), _ptr(dists, hold),
+                                              counts.data_ptr() if counts is not None else None)
+        if rc < 0:
+            raise ValueError("annhip_query_sorted_set refused k=%d split=%d (see its line on stderr)" % (kq, split))
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in (lo, hi, rad, ids, dists, counts, hold):
+                if t is not None:
+                    t.record_stream(stream)
+        entries = int(rc)
+        if not split:  # the library counted every interval slot; the non-empty runs, without waiting for them
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(y.device)):
+                entries = (self.tag_runs_set((where[0], off, lo, hi))[1] != 0).sum()
+        return (ids, dists, entries) if rad is None else (ids, dists, counts, entries)
 
     def query_routed(self, y, where, scan_below=None, k=None, alias=False, ws=None, stream=None, out_ids=None, out_dists=None):
         """query(y, where=where, k=k) with a router in front -> (ids int64 [Q,k], sq dists [Q,k], rc).  scan_below=None is

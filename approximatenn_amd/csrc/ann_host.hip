@@ -276,8 +276,16 @@ struct annhip_workspace {
   DevBuf pbits;  // fixed mode with pair bits: u8[Q][T][b] ranked projection indices of this batch (annhip_index_set_probe)
   DevBuf sorted;  // annhip_query_sorted: u32 start[Q], len[Q], list[Q][3], qmask[Q]
   DevBuf tie_d, tie_i;  // pruned stage 1: [Q][k+1] exact candidate lists of the flagged queries (PruneArgs::tie_d / tie_i)
+  // annhip_query_sorted_set: the staging that the interval count sizes, the arrays that the entry count sizes, and the
+  // pinned copy of the call's offsets with the event that says the previous call's upload has read it
+  DevBuf sset, spart;
+  PinBuf spin;
+  hipEvent_t sset_ev = NULL;
   u32 *d_fcount = NULL;
   void release() {
+    sset.release(), spart.release(), spin.release();
+    if (sset_ev) HIPCHECK(hipEventDestroy(sset_ev));
+    sset_ev = NULL;
     DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted, &tie_d, &tie_i};
     for (DevBuf *b : bufs) b->release();
     if (d_fcount) HIPCHECK(hipFree(d_fcount));
@@ -3112,8 +3120,9 @@ extern "C" int annhip_tag_runs(annhip_index *ix, void *hip_stream, size_t ycnt, 
 }
 
 // the scan's launch for this index's row length: false where a row is too long for the LDS of one CU
+// part != NULL: the set form -- list has four words per entry and entry e's result goes to part[slot(e)][k]
 static bool launch_sorted_scan(annhip_index *ix, size_t Q, const FT *y, int alias, size_t k, const u32 *list, size_t *ids, FT *dists,
-                               hipStream_t s, bool dry) {
+                               hipStream_t s, bool dry, Key *part = NULL) {
   const size_t d = ix->d;
   const ExValid valid = ix->filter ? EX_BITS : EX_ALL;
   SortedArgs SA;
@@ -3135,9 +3144,14 @@ static bool launch_sorted_scan(annhip_index *ix, size_t Q, const FT *y, int alia
   if (layout_is_generic(code)) {
     const ExShape sh = shape(true, ANN_EX_GEN_WAVES);
     if (!ok || dry) return ok;
-    allow_lds(sorted_scan_generic_kernel, sh.smem);
-    hipLaunchKernelGGL(sorted_scan_generic_kernel, dim3((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))),
-                       dim3((unsigned)(64 * sh.W)), sh.smem, s, SA);
+    const dim3 grid((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))), block((unsigned)(64 * sh.W));
+    if (part) {
+      allow_lds(sorted_scan_generic_kernel<true>, sh.smem);
+      hipLaunchKernelGGL(sorted_scan_generic_kernel<true>, grid, block, sh.smem, s, SortedSetArgs{SA, part});
+    } else {
+      allow_lds(sorted_scan_generic_kernel<false>, sh.smem);
+      hipLaunchKernelGGL(sorted_scan_generic_kernel<false>, grid, block, sh.smem, s, SA);
+    }
   } else {
     with_value(QueryLayouts{}, code, [&](auto dc) {
       constexpr int D = decltype(dc)::value;
@@ -3145,12 +3159,14 @@ static bool launch_sorted_scan(annhip_index *ix, size_t Q, const FT *y, int alia
         const ExShape sh = shape(false, ExCfg<D>::WAVES);
         if (!ok || dry) return;
         const dim3 grid((unsigned)((Q + sh.W * ANN_EX_QB - 1) / (sh.W * ANN_EX_QB))), block((unsigned)(64 * sh.W));
-        auto go = [&](auto kernel) {
+        auto go = [&](auto kernel, auto args) {
           allow_lds(kernel, sh.smem);
-          hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, SA);
+          hipLaunchKernelGGL(kernel, grid, block, sh.smem, s, args);
         };
-        if (valid == EX_BITS) go(sorted_scan_kernel<D, EX_BITS>);
-        else go(sorted_scan_kernel<D, EX_ALL>);
+        if (part && valid == EX_BITS) go(sorted_scan_kernel<D, EX_BITS, true>, SortedSetArgs{SA, part});
+        else if (part) go(sorted_scan_kernel<D, EX_ALL, true>, SortedSetArgs{SA, part});
+        else if (valid == EX_BITS) go(sorted_scan_kernel<D, EX_BITS, false>, SA);
+        else go(sorted_scan_kernel<D, EX_ALL, false>, SA);
       }
     });
   }
@@ -3191,6 +3207,158 @@ extern "C" long annhip_query_sorted(annhip_index *ix, annhip_workspace *ws, void
   }
   if (radius_dev) launch_radius_trim(ycnt, kq, nt, reinterpret_cast<const FT *>(radius_dev), ids_dev, dd, counts_dev, s);
   return 0;
+}
+
+// ----------------------------------------------------------------------------- sets of intervals (annhip_query_sorted_set)
+// Contract: include/ann_hip.h.  Kernels: the end of ann_sorted_kernels.h.
+static const char *set_offsets_refusal(size_t ycnt, const uint32_t *off) {
+  if (off[0] != 0) return "off_host[0] must be 0";
+  for (size_t q = 0; q < ycnt; q++) {
+    if (off[q + 1] < off[q]) return "off_host must not decrease";
+    if (off[q + 1] - off[q] > ANN_SET_MAX) return "a query has more than 256 intervals";
+  }
+  return NULL;
+}
+// the call's offsets -> doff on s, through the workspace's pinned buffer: waits for the previous call's upload only
+static void set_upload_offsets(annhip_workspace &w, size_t ycnt, const uint32_t *off_host, u32 *doff, hipStream_t s) {
+  if (w.sset_ev) HIPCHECK(hipEventSynchronize(w.sset_ev));
+  else HIPCHECK(hipEventCreateWithFlags(&w.sset_ev, hipEventDisableTiming));
+  const size_t bytes = sizeof(u32) * (ycnt + 1);
+  void *pin = w.spin.need(bytes);
+  memcpy(pin, off_host, bytes);
+  HIPCHECK(hipMemcpyAsync(doff, pin, bytes, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(w.sset_ev, s));
+}
+static void launch_set_runs(const annhip_index *ix, size_t Q, const u32 *doff, const u32 *lo, const u32 *hi, u32 S, u32 *nlo, u32 *nhi,
+                            u32 *start, u32 *len, u32 *qof, u32 *cnt, hipStream_t s) {
+  hipLaunchKernelGGL(set_runs_kernel, dim3(grid_for(Q, 64, 1u << 30)), dim3(64), 0, s, ix->ord_keys, (u32)ix->ord_ms, (u32)Q, doff, lo, hi,
+                     S, nlo, nhi, start, len, qof, cnt);
+  HIPCHECK(hipGetLastError());
+}
+
+extern "C" int annhip_tag_runs_set(annhip_index *ix, void *hip_stream, size_t ycnt, const uint32_t *off_host, const uint32_t *lo_dev,
+                                   const uint32_t *hi_dev, uint32_t *start_dev, uint32_t *len_dev) {
+  const char *why = !ix->ord_perm ? "the index has no tag order (annhip_index_sort_tags)"
+                    : !off_host || !lo_dev || !hi_dev || !start_dev || !len_dev ? "off_host, lo_dev, hi_dev, start_dev and len_dev must all be given"
+                    : ycnt >= 0xFFFFFFF0ull ? "query batch too large" : set_offsets_refusal(ycnt, off_host);
+  if (why) {
+    fprintf(stderr, "annhip_tag_runs_set: %s\n", why);
+    return -1;
+  }
+  if (!ycnt || !off_host[ycnt]) return 0;
+  hipStream_t s = (hipStream_t)hip_stream;
+  u32 *doff = (u32 *)ix->ws.sset.need(sizeof(u32) * (ycnt + 1));
+  set_upload_offsets(ix->ws, ycnt, off_host, doff, s);
+  launch_set_runs(ix, ycnt, doff, lo_dev, hi_dev, 0, NULL, NULL, start_dev, len_dev, NULL, NULL, s);
+  return 0;
+}
+
+extern "C" long annhip_query_sorted_set(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev,
+                                        int alias, size_t kq, const ftype *radius_dev, const uint32_t *off_host,
+                                        const uint32_t *lo_dev, const uint32_t *hi_dev, size_t split_rows, size_t *ids_dev,
+                                        ftype *dists_dev, uint32_t *counts_dev) {
+  const size_t nt = n_total(ix), slots_max = (size_t)1 << 27;
+  const char *why = !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                    : !ix->ord_perm ? "the index has no tag order (annhip_index_sort_tags)"
+                    : !y_dev || !off_host || !lo_dev || !hi_dev || !ids_dev || !dists_dev
+                        ? "y_dev, off_host, lo_dev, hi_dev, ids_dev and dists_dev must all be given"
+                    : kq < 1 || kq > 1024 ? "kq must be in 1..1024"
+                    : kq > nt - (alias && nt ? 1 : 0) ? "kq exceeds the number of rows a query can be given"
+                    : ycnt >= 0xFFFFFFF0ull / 4 ? "query batch too large"
+                    : (split_rows && split_rows < 64) || split_rows > 0xFFFFFFFFull ? "split_rows must be 0 or in 64..2^32-1"
+                    : !launch_sorted_scan(ix, ycnt, NULL, alias, kq, NULL, NULL, NULL, 0, true) ? "row too long for the LDS of one CU"
+                                                                                                 : set_offsets_refusal(ycnt, off_host);
+  const size_t T = why ? 0 : off_host[ycnt];  // interval slots
+  if (!why && !split_rows && T * kq > slots_max) why = "more than 2^27 partial slots (entries x kq)";
+  if (why) {
+    fprintf(stderr, "annhip_query_sorted_set: %s\n", why);
+    return -2;
+  }
+  if (!ycnt) return 0;
+  hipStream_t s = (hipStream_t)hip_stream;
+  annhip_workspace &w = ws ? *ws : ix->ws;
+  const FT *y = reinterpret_cast<const FT *>(y_dev);
+  FT *dd = reinterpret_cast<FT *>(dists_dev);
+  const u32 S = (u32)split_rows;
+  size_t maxset = 0;
+  for (size_t q = 0; q < ycnt; q++) maxset = std::max<size_t>(maxset, off_host[q + 1] - off_host[q]);
+  // staging sized by the interval count: off[Q + 1], nlo / nhi / start / len / qof [T], cnt -> eoff [T + 1], qmask / rlo / rhi [Q]
+  u32 *doff = (u32 *)w.sset.need(sizeof(u32) * ((ycnt + 1) + 6 * T + 1 + 3 * ycnt));
+  u32 *nlo = doff + ycnt + 1, *nhi = nlo + T, *start = nhi + T, *len = start + T, *qof = len + T, *cnt = qof + T;
+  u32 *qmask = cnt + T + 1, *rlo = qmask + ycnt, *rhi = rlo + ycnt;
+  set_upload_offsets(w, ycnt, off_host, doff, s);
+  size_t E = T;
+  if (T) {
+    launch_set_runs(ix, ycnt, doff, lo_dev, hi_dev, S, nlo, nhi, start, len, qof, cnt, s);
+    if (S) {  // eoff := the exclusive prefix sums of the piece counts; E = eoff[T] comes back to the host
+      u32 e32 = 0;
+      HIPCHECK(hipMemsetAsync(cnt + T, 0, sizeof(u32), s));
+      hipLaunchKernelGGL(tsort_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, T + 1);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipMemcpyAsync(&e32, cnt + T, sizeof e32, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipStreamSynchronize(s));
+      E = e32;
+      if (E * kq > slots_max || E >= 0xFFFFFFF0ull / 4) {
+        fprintf(stderr, "annhip_query_sorted_set: more than 2^27 partial slots (entries x kq)\n");
+        return -2;
+      }
+    }
+  }
+  const u32 *eoff = S ? cnt : NULL;
+  Key *part = NULL;
+  u32 *head = NULL;
+  // sized by the entry count and the batch (w.spart): the partial lists first (16-byte aligned), then -- where rows have
+  // been appended since the sort -- two rows of kq per query twice (a second result and one rank's fresh rows), then eq /
+  // es / ee / head [E], two (key, slot) pairs of arrays for the sort, its histogram, the list
+  const bool fresh = nt > ix->ord_ms && maxset;
+  const u32 nblk = (u32)((E + ANN_SORT_ITEMS - 1) / ANN_SORT_ITEMS);
+  const size_t part_bytes = (sizeof(Key) * E * kq + 15) & ~(size_t)15;
+  const size_t row_i = sizeof(size_t) * ycnt * kq, row_d = (sizeof(FT) * ycnt * kq + 15) & ~(size_t)15;
+  unsigned char *base = (unsigned char *)w.spart.need(part_bytes + (fresh ? 2 * (row_i + row_d) : 0) +
+                                                      sizeof(u32) * (12 * E + (size_t)256 * nblk));
+  size_t *tmp_i = reinterpret_cast<size_t *>(base + part_bytes), *fr_i = reinterpret_cast<size_t *>(base + part_bytes + row_i);
+  FT *tmp_d = reinterpret_cast<FT *>(base + part_bytes + 2 * row_i), *fr_d = reinterpret_cast<FT *>(base + part_bytes + 2 * row_i + row_d);
+  if (E) {
+    part = reinterpret_cast<Key *>(base);
+    u32 *eq = reinterpret_cast<u32 *>(base + part_bytes + (fresh ? 2 * (row_i + row_d) : 0)), *es = eq + E, *ee = es + E;
+    head = ee + E;
+    u32 *k0 = head + E, *v0 = k0 + E, *k1 = v0 + E, *v1 = k1 + E, *hist = v1 + E, *list = hist + (size_t)256 * nblk;
+    hipLaunchKernelGGL(set_pieces_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, (u32)T, start, len, qof, eoff, S, eq, es, ee);
+    HIPCHECK(hipMemsetAsync(head, 0, sizeof(u32) * E, s));
+    hipLaunchKernelGGL(tsort_init_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, s, (u32)E, es, 0xFFFFFFFFu, k0, v0);
+    for (int shift = 0; shift < 32 && ((u64)ix->ord_ms >> shift); shift += 8) {  // a start is at most ord_ms
+      hipLaunchKernelGGL(tsort_count_kernel, dim3(nblk), dim3(64), 0, s, k0, (u32)E, shift, nblk, hist);
+      hipLaunchKernelGGL(tsort_scan_kernel, dim3(1), dim3(1024), 0, s, hist, (size_t)256 * nblk);
+      hipLaunchKernelGGL(tsort_place_kernel, dim3(nblk), dim3(64), 0, s, k0, v0, (u32)E, shift, nblk, hist, k1, v1);
+      std::swap(k0, k1), std::swap(v0, v1);
+    }
+    hipLaunchKernelGGL(set_list_kernel, dim3(grid_for(E, 256, 4096)), dim3(256), 0, s, (u32)E, v0, eq, es, ee, list);
+    HIPCHECK(hipGetLastError());
+    launch_sorted_scan(ix, E, y, alias, kq, list, NULL, NULL, s, false, part);
+  }
+  // The rows appended since the sort compete once per interval rank (the intervals of a query are disjoint): their scan
+  // under rank r's intervals, from nothing, then a two-row merge into the running result.  The result alternates between
+  // the output and a second buffer; the merge of the partial lists starts where an even count of steps is left.
+  size_t *cur_i = fresh && (maxset & 1) ? tmp_i : ids_dev, *oth_i = cur_i == ids_dev ? tmp_i : ids_dev;
+  FT *cur_d = cur_i == ids_dev ? dd : tmp_d, *oth_d = cur_i == ids_dev ? tmp_d : dd;
+  hipLaunchKernelGGL(sorted_set_merge_kernel, dim3((unsigned)((ycnt + 3) / 4)), dim3(256), 0, s, part, head, (u32)ycnt, doff, eoff,
+                     (int)kq, nt, cur_i, cur_d);
+  HIPCHECK(hipGetLastError());
+  if (fresh) {
+    sorted_fill_kernel<<<grid_for(ycnt, 256, 1024), 256, 0, s>>>((u32)ycnt, ix->ord_mask, qmask);
+    const TagQuery tq{ix->tags, qmask, rlo, rhi};
+    for (size_t r = 0; r < maxset; r++) {
+      hipLaunchKernelGGL(set_rank_kernel, dim3(grid_for(ycnt, 256, 1u << 30)), dim3(256), 0, s, (u32)ycnt, (u32)r, doff, nlo, nhi, rlo, rhi);
+      HIPCHECK(hipGetLastError());
+      launch_tail_merge(ix, ycnt, y, alias, kq, &tq, 0, NULL, NULL, fr_i, fr_d, NULL, s, ix->ord_ms - ix->n);
+      hipLaunchKernelGGL(set_merge2_kernel, dim3((unsigned)((ycnt + 3) / 4)), dim3(256), 0, s, (u32)ycnt, (int)kq, nt, cur_i, cur_d, fr_i,
+                         fr_d, oth_i, oth_d);
+      HIPCHECK(hipGetLastError());
+      std::swap(cur_i, oth_i), std::swap(cur_d, oth_d);
+    }
+  }
+  if (radius_dev) launch_radius_trim(ycnt, kq, nt, reinterpret_cast<const FT *>(radius_dev), ids_dev, dd, counts_dev, s);
+  return (long)E;
 }
 
 // ----------------------------------------------------------------------------- rerank (annhip_rerank)

@@ -1,5 +1,5 @@
 // ann_sorted_kernels.h -- the tag order of an index and the exact scan of its runs (annhip_index_sort_tags,
-// annhip_tag_runs, annhip_query_sorted; gfx950).
+// annhip_tag_runs, annhip_query_sorted, annhip_tag_runs_set, annhip_query_sorted_set; gfx950).
 //
 // The order: perm[ms] = the row ids sorted by (tags[id] & field_mask, id), keys[ms] = the masked words in that order.  A
 // predicate qlo <= (tag & field_mask) <= qhi then selects ONE contiguous run [start, end) of positions of the order, found
@@ -25,6 +25,9 @@
 //
 // Known limit: one workgroup streams a whole span, so a single query whose run is millions of rows runs on one CU.
 // Long runs are not split over workgroups; such queries belong on the ANN path (Index.query_routed(scan_below=)).
+// That remains true of annhip_query_sorted.  annhip_query_sorted_set (the end of this file) lets a query own several entries
+// of the list -- one per interval of its set, or one per piece of a run cut at global multiples of split_rows -- so its
+// long runs ARE split over workgroups: the entries' results go to partial lists and sorted_set_merge_kernel merges them.
 // LDS carve-up: exact_shape(..., sorted = true) on the host: tile, per-wave buffers, then the tile's ids, its flags and the
 // workgroup's (q, start, end) triples.  No register prefetch of the next tile.
 #pragma once
@@ -172,10 +175,12 @@ struct SortedArgs {
 
 // the workgroup's entries of the ordered list -> trip[0..G) = q, [G..2G) = start, [2G..3G) = end; an entry beyond the list
 // repeats the last query with an empty run (its loads stay inside y; nothing is admitted for it)
+// LS: words per list entry -- 3, or 4 in the set form, whose fourth word (the entry's slot) stays in global memory
+template <int LS>
 __device__ __forceinline__ void sorted_load_list(const SortedArgs &SA, u32 *trip, u32 G, u32 e0, u32 ne) {
   for (u32 i = threadIdx.x; i < G; i += blockDim.x) {
     const bool live = i < ne;
-    const u32 *src = SA.list + 3 * (size_t)(e0 + (live ? i : ne - 1));
+    const u32 *src = SA.list + LS * (size_t)(e0 + (live ? i : ne - 1));
     trip[i] = src[0];
     trip[G + i] = live ? src[1] : 0;
     trip[2 * G + i] = live ? src[2] : 0;
@@ -212,10 +217,38 @@ __device__ __forceinline__ void sorted_gather_tile(const SortedArgs &SA, FT *til
   }
 }
 
-template <int D, int V>
-__global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void sorted_scan_kernel(SortedArgs SA) {
+// the k best of query I of an entry of the set form, ascending, key_max() where the piece had fewer rows -> the entry's
+// slot of the partial lists [E][k] (ExSel::store's format)
+template <int I>
+__device__ __forceinline__ void set_store(ExSel &S, const TailArgs &A, Key *part, u32 slot, bool live) {
+  if (!live) return;
+  const int lane = lane_id();
+  Key *b = S.buf + (size_t)I * S.cap;
+  const int c = ex_compact(b, S.cnt[I], A.k, S.out);
+  Key *dst = part + (size_t)slot * A.k;
+  for (int j = lane; j < A.k; j += ANN_WAVE) dst[j] = j < c ? b[j] : key_max();
+}
+
+// SET (annhip_query_sorted_set): the list has four words per entry and entry e's result goes to part[slot(e)], not to the
+// output row of its query; everything else is the same code.
+struct SortedSetArgs {
+  SortedArgs s;  // s.list: [E][4] = (q, start, end, slot), ascending by start; s.t.Q = E; s.t.out_ids / out_d unused
+  Key *part;     // [E][k]
+};
+template <bool SET>
+using SortedKernelArgs = std::conditional_t<SET, SortedSetArgs, SortedArgs>;
+__device__ __forceinline__ const SortedArgs &sorted_args(const SortedArgs &a) { return a; }
+__device__ __forceinline__ const SortedArgs &sorted_args(const SortedSetArgs &a) { return a.s; }
+__device__ __forceinline__ Key *sorted_part(const SortedArgs &) { return NULL; }
+__device__ __forceinline__ Key *sorted_part(const SortedSetArgs &a) { return a.part; }
+
+template <int D, int V, bool SET = false>
+__global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void sorted_scan_kernel(SortedKernelArgs<SET> SX) {
+  const SortedArgs &SA = sorted_args(SX);
+  Key *part = sorted_part(SX);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int C = RowChunks<D>::C;
+  constexpr int LS = SET ? 4 : 3;
   const TailArgs &A = SA.t;
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
   const int d = A.d;
@@ -226,7 +259,7 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void sorted_scan_kernel(Sorte
   u32 *tflag = tids + A.tile_rows;
   u32 *trip = tflag + A.tile_rows;
   const u32 G = (u32)W * ANN_EX_QB, e0 = blockIdx.x * G, ne = min(G, A.Q - e0);
-  sorted_load_list(SA, trip, G, e0, ne);
+  sorted_load_list<LS>(SA, trip, G, e0, ne);
   __syncthreads();
   // first entry of this wave; wave-uniform, which the compiler cannot see: scalar registers, and so are the wave's four
   // (q, start, end)
@@ -305,18 +338,29 @@ __global__ __launch_bounds__(64 * ExCfg<D>::WAVES) void sorted_scan_kernel(Sorte
       }
     }
   }
-  tail_store<0>(S, A, qi[0], ebase + 0 < ne);
-  tail_store<1>(S, A, qi[1], ebase + 1 < ne);
-  tail_store<2>(S, A, qi[2], ebase + 2 < ne);
-  tail_store<3>(S, A, qi[3], ebase + 3 < ne);
+  if constexpr (SET) {
+#define ANN_SET_STORE(I) \
+  if (ebase + (I) < ne) set_store<I>(S, A, part, __builtin_amdgcn_readfirstlane(SA.list[LS * (size_t)(e0 + ebase + (I)) + 3]), true);
+    ANN_SET_STORE(0) ANN_SET_STORE(1) ANN_SET_STORE(2) ANN_SET_STORE(3)
+#undef ANN_SET_STORE
+  } else {
+    tail_store<0>(S, A, qi[0], ebase + 0 < ne);
+    tail_store<1>(S, A, qi[1], ebase + 1 < ne);
+    tail_store<2>(S, A, qi[2], ebase + 2 < ne);
+    tail_store<3>(S, A, qi[3], ebase + 3 < ne);
+  }
   if (A.scored && threadIdx.x == 0 && nf) atomicAdd(&A.scored[(blockIdx.x & 63u) * 8u], (unsigned long long)nf);
 }
 static_assert(ANN_EX_QB == 4, "sorted_scan_kernel names its four queries");
 
 // Any d without a register layout: tail_merge_generic_kernel's literal in-place tree over the spans of the order.  V is a
 // kernel argument here (bits NULL or not): this form is bound by its LDS tree.
-__global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void sorted_scan_generic_kernel(SortedArgs SA) {
+template <bool SET = false>
+__global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void sorted_scan_generic_kernel(SortedKernelArgs<SET> SX) {
+  const SortedArgs &SA = sorted_args(SX);
+  Key *part = sorted_part(SX);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int LS = SET ? 4 : 3;
   const TailArgs &A = SA.t;
   const int lane = lane_id(), w = threadIdx.x >> 6, W = blockDim.x >> 6;
   const int d = A.d;
@@ -334,7 +378,7 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void sorted_scan_generic_ker
   u32 *trip = tflag + A.tile_rows;
   const bool bits = A.bits != NULL;
   const u32 G = (u32)W * ANN_EX_QB, e0 = blockIdx.x * G, ne = min(G, A.Q - e0);
-  sorted_load_list(SA, trip, G, e0, ne);
+  sorted_load_list<LS>(SA, trip, G, e0, ne);
   __syncthreads();
   const u32 ebase = __builtin_amdgcn_readfirstlane((u32)w * ANN_EX_QB);
   ExSel S;
@@ -382,9 +426,194 @@ __global__ __launch_bounds__(64 * ANN_EX_GEN_WAVES) void sorted_scan_generic_ker
 #undef ANN_SORTED_GEN_QUERY
     }
   }
-#define ANN_SORTED_GEN_STORE(I) \
-  tail_store<I>(S, A, __builtin_amdgcn_readfirstlane(trip[ebase + (I)]), ebase + (I) < ne);
+#define ANN_SORTED_GEN_STORE(I)                                                                                          \
+  if constexpr (SET) {                                                                                                   \
+    if (ebase + (I) < ne)                                                                                                \
+      set_store<I>(S, A, part, __builtin_amdgcn_readfirstlane(SA.list[LS * (size_t)(e0 + ebase + (I)) + 3]), true);      \
+  } else {                                                                                                               \
+    tail_store<I>(S, A, __builtin_amdgcn_readfirstlane(trip[ebase + (I)]), ebase + (I) < ne);                            \
+  }
   ANN_SORTED_GEN_STORE(0) ANN_SORTED_GEN_STORE(1) ANN_SORTED_GEN_STORE(2) ANN_SORTED_GEN_STORE(3)
 #undef ANN_SORTED_GEN_STORE
   if (A.scored && threadIdx.x == 0 && nf) atomicAdd(&A.scored[(blockIdx.x & 63u) * 8u], (unsigned long long)nf);
+}
+
+// ------------------------------------------------------------------------------------------ sets of intervals
+// annhip_tag_runs_set / annhip_query_sorted_set (include/ann_hip.h).  Query q owns the intervals [off[q], off[q + 1]) of
+// (lo, hi); they are normalised to pairwise disjoint ones, every non-empty run becomes one list entry or -- cut at the
+// global positions S, 2S, ... of the order -- several, the entries are ordered by start (tsort_count / scan / place with
+// the start as key and the slot as value: ties stay in creation order), scanned by the set form of the scan above into
+// part[E][k], and merged per query.  The slots of one query are consecutive: [eoff[off[q]], eoff[off[q + 1]]).
+#define ANN_SET_MAX 256  // intervals per query
+
+// One thread per query.  Its intervals, copied to start / len, are ordered there by (lo, hi); empty ones and those covered
+// by an earlier one become (1, 0), the others are clipped to begin above the largest hi before them (nothing follows
+// hi = 0xFFFFFFFF: hi + 1 is never formed then).  nlo / nhi (may be NULL) := the normalised intervals; start / len := their
+// runs as tag_runs_kernel finds them, (0, 0) for the emptied slots; qof (may be NULL) := q; cnt (may be NULL) := the list
+// entries of the slot: 1 with S = 0, else the pieces of a non-empty run.
+__global__ void set_runs_kernel(const u32 *__restrict__ keys, u32 ms, u32 Q, const u32 *__restrict__ off, const u32 *__restrict__ lo,
+                                const u32 *__restrict__ hi, u32 S, u32 *__restrict__ nlo, u32 *__restrict__ nhi, u32 *start, u32 *len,
+                                u32 *__restrict__ qof, u32 *__restrict__ cnt) {
+  const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= Q) return;
+  const u32 a = off[q], b = off[q + 1];
+  for (u32 j = a; j < b; j++) {  // insertion sort by (lo, hi): at most ANN_SET_MAX items
+    const u32 l = lo[j], h = hi[j];
+    u32 i = j;
+    while (i > a && (start[i - 1] > l || (start[i - 1] == l && len[i - 1] > h))) {
+      start[i] = start[i - 1], len[i] = len[i - 1];
+      i--;
+    }
+    start[i] = l, len[i] = h;
+  }
+  bool any = false, full = false;
+  u32 top = 0;  // the largest hi so far
+  for (u32 j = a; j < b; j++) {
+    u32 l = start[j], h = len[j];
+    bool live = l <= h && !full;
+    if (live && any) {
+      if (h <= top) live = false;
+      else l = max(l, top + 1);  // top < 0xFFFFFFFF: not full
+    }
+    if (live) any = true, top = h, full = h == 0xFFFFFFFFu;
+    else l = 1, h = 0;
+    if (nlo) nlo[j] = l, nhi[j] = h;
+    u32 s = 0, n = 0;
+    if (live) {
+      u32 x = 0, y = ms;
+      while (x < y) {
+        const u32 mid = x + ((y - x) >> 1);
+        if (keys[mid] < l) x = mid + 1;
+        else y = mid;
+      }
+      s = x, y = ms;
+      while (x < y) {
+        const u32 mid = x + ((y - x) >> 1);
+        if (keys[mid] <= h) x = mid + 1;
+        else y = mid;
+      }
+      n = x - s;
+    }
+    start[j] = s, len[j] = n;
+    if (qof) qof[j] = q;
+    if (cnt) cnt[j] = !S ? 1u : !n ? 0u : (s + n - 1) / S - s / S + 1;
+  }
+}
+
+// One wave per interval slot j: its entries (q, start, end) to slots eoff[j] ...  S = 0: one entry, the run itself (an empty
+// run is an entry that admits nothing).  S > 0: the pieces [max(s, tS), min(e, (t + 1)S)) of a non-empty run.
+__global__ __launch_bounds__(256) void set_pieces_kernel(u32 T, const u32 *__restrict__ start, const u32 *__restrict__ len,
+                                                          const u32 *__restrict__ qof, const u32 *__restrict__ eoff, u32 S,
+                                                          u32 *__restrict__ eq, u32 *__restrict__ es, u32 *__restrict__ ee) {
+  const u32 lane = lane_id(), j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (j >= T) return;
+  const u32 s = start[j], n = len[j], q = qof[j];
+  if (!S) {
+    if (lane == 0) eq[j] = q, es[j] = s, ee[j] = s + n;
+    return;
+  }
+  if (!n) return;
+  const u32 e = s + n, base = eoff[j], first = s / S, np = (e - 1) / S - first + 1;
+  for (u32 p = lane; p < np; p += ANN_WAVE) {
+    const u64 ps = (u64)(first + p) * S, pe = ps + S;
+    eq[base + p] = q, es[base + p] = max(s, (u32)ps), ee[base + p] = pe < (u64)e ? (u32)pe : e;
+  }
+}
+
+// list[r] := (q, start, end, slot) of the slot that the sort put at rank r
+__global__ void set_list_kernel(u32 E, const u32 *__restrict__ slots, const u32 *__restrict__ eq, const u32 *__restrict__ es,
+                                const u32 *__restrict__ ee, u32 *__restrict__ list) {
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < E; r += (size_t)gridDim.x * blockDim.x) {
+    const u32 v = slots[r];
+    list[4 * r] = eq[v], list[4 * r + 1] = es[v], list[4 * r + 2] = ee[v], list[4 * r + 3] = v;
+  }
+}
+
+// the intervals of rank r of every query for the scan of the rows appended after the sort: (1, 0) where the set is shorter
+__global__ void set_rank_kernel(u32 Q, u32 r, const u32 *__restrict__ off, const u32 *__restrict__ nlo, const u32 *__restrict__ nhi,
+                                u32 *__restrict__ rlo, u32 *__restrict__ rhi) {
+  const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= Q) return;
+  const u32 a = off[q], b = off[q + 1];
+  const bool has = r < b - a;
+  rlo[q] = has ? nlo[a + r] : 1u, rhi[q] = has ? nhi[a + r] : 0u;
+}
+
+// One wave per query: the k smallest keys of its partial lists part[e0 .. e1)[k], ascending, unpacked to the output row,
+// pad (pad_id, +inf).  Every list is ascending with key_max() last, and the keys are distinct across lists (the pieces
+// are disjoint positions of the order).  Lane l owns the lists e0 + l, e0 + l + 64, ...; head[e] (zeroed by the host) is
+// how many keys of list e are out; a lane holds the smallest head key of its lists, and each of the k rounds takes the
+// wave's smallest and advances that one list.  eoff == NULL: slot j is entry j (S = 0).
+__global__ __launch_bounds__(256) void sorted_set_merge_kernel(const Key *__restrict__ part, u32 *__restrict__ head, u32 Q,
+                                                                const u32 *__restrict__ off, const u32 *__restrict__ eoff, int k,
+                                                                size_t pad_id, size_t *__restrict__ ids, FT *__restrict__ dists) {
+  const u32 lane = lane_id();
+  const u32 q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (q >= Q) return;
+  const u32 e0 = eoff ? eoff[off[q]] : off[q], e1 = eoff ? eoff[off[q + 1]] : off[q + 1];
+  size_t *io = ids + (size_t)q * k;
+  FT *dout = dists + (size_t)q * k;
+  Key cur = key_max();
+  u32 mine = 0;  // the list cur came from
+  for (u32 e = e0 + lane; e < e1; e += ANN_WAVE) {
+    const Key c = part[(size_t)e * k];
+    if (key_less(c, cur)) cur = c, mine = e;
+  }
+  for (int j = 0; j < k; j++) {
+    const Key best = wave_min_key(cur);
+    const bool none = key_eq(best, key_max());  // wave-uniform
+    if (lane == 0) io[j] = none ? pad_id : (size_t)key_id(best), dout[j] = none ? ft_inf() : key_dist(best);
+    if (none) continue;
+    if (key_eq(cur, best)) {  // one lane: the keys are distinct
+      head[mine]++;
+      cur = key_max();
+      for (u32 e = e0 + lane; e < e1; e += ANN_WAVE) {
+        const u32 h = head[e];
+        const Key c = h < (u32)k ? part[(size_t)e * k + h] : key_max();
+        if (key_less(c, cur)) cur = c, mine = e;
+      }
+    }
+  }
+}
+
+// One wave per query: C := the k smallest of A and B, two ascending rows of k (ids, distances) padded with (pad_id, +inf)
+// whose keys are distinct, in the same format.  An entry's place is its index plus the entries of the other row below it.
+// C is neither A nor B.  (The rows appended after the sort: tail_merge_kernel cannot take the running row as its seed
+// twice -- it drops seed entries whose id lies in the range it scans -- so every interval rank is scanned from nothing
+// and merged here.)
+__global__ __launch_bounds__(256) void set_merge2_kernel(u32 Q, int k, size_t pad_id, const size_t *__restrict__ a_ids,
+                                                          const FT *__restrict__ a_d, const size_t *__restrict__ b_ids,
+                                                          const FT *__restrict__ b_d, size_t *__restrict__ c_ids, FT *__restrict__ c_d) {
+  const int lane = lane_id();
+  const u32 q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (q >= Q) return;
+  const size_t *ai = a_ids + (size_t)q * k, *bi = b_ids + (size_t)q * k;
+  const FT *ad = a_d + (size_t)q * k, *bd = b_d + (size_t)q * k;
+  size_t *ci = c_ids + (size_t)q * k;
+  FT *cd = c_d + (size_t)q * k;
+  auto live = [&](const size_t *ids) {  // the entries before the pads
+    int lo = 0, hi = k;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ids[mid] != pad_id) lo = mid + 1;
+      else hi = mid;
+    }
+    return lo;
+  };
+  const int ca = live(ai), cb = live(bi);
+  auto place = [&](const size_t *xi, const FT *xd, int cx, const size_t *oi, const FT *od, int co) {
+    for (int i = lane; i < cx; i += ANN_WAVE) {
+      const Key x = key_make(xd[i], (u32)xi[i]);
+      int lo = 0, hi = co;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key_less(key_make(od[mid], (u32)oi[mid]), x)) lo = mid + 1;
+        else hi = mid;
+      }
+      if (i + lo < k) ci[i + lo] = xi[i], cd[i + lo] = xd[i];
+    }
+  };
+  place(ai, ad, ca, bi, bd, cb);
+  place(bi, bd, cb, ai, ad, ca);
+  for (int j = ca + cb + lane; j < k; j += ANN_WAVE) ci[j] = pad_id, cd[j] = ft_inf();
 }

@@ -718,7 +718,8 @@ int annhip_exact_knn_between(size_t n, size_t d, size_t k, const ftype *points_d
  * per row and tile fill).
  * Limits: one order and one mask per index; native rows only; the order is not saved in index files; parity mode,
  * sharded indexes and annhip_stream_* do not use it; long runs are not split -- one workgroup streams a whole span of
- * overlapping runs, so a single query whose run is millions of rows runs on one CU: keep such queries on the ANN path. */
+ * overlapping runs, so a single query whose run is millions of rows runs on one CU: keep such queries on the ANN path, or
+ * give them to annhip_query_sorted_set with split_rows > 0, which splits. */
 int annhip_index_sort_tags(annhip_index *ix, uint32_t field_mask /* 0: drop the order */);
 size_t annhip_index_tag_order(const annhip_index *ix, uint32_t *field_mask /* may be NULL */);
 int annhip_tag_runs(annhip_index *ix, void *hip_stream, size_t ycnt, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
@@ -726,6 +727,47 @@ int annhip_tag_runs(annhip_index *ix, void *hip_stream, size_t ycnt, const uint3
 long annhip_query_sorted(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
                          size_t kq, const ftype *radius_dev /* may be NULL */, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
                          size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev /* written iff radius_dev != NULL */);
+
+/* ---- the tag order: sets of intervals per query, long runs split over workgroups --------------------- */
+/* annhip_query_sorted_set is annhip_query_sorted for a query whose predicate is a UNION of intervals: query q owns the
+ * intervals j in [off[q], off[q + 1]) of (lo[j], hi[j]), and row i competes for it iff
+ * lo[j] <= (tags[i] & field_mask) <= hi[j] for some such j.  Every other rule is annhip_query_sorted's: the allow list,
+ * alias, the NATIVE rows, the pads (n_total, +inf), the rows appended after the sort (they compete exactly once), the
+ * radius trim and its counts, the workspace and the stream.  A query with no interval matches nothing and gets all pads.
+ * off_host is a HOST array [ycnt + 1], off_host[0] = 0, non-decreasing; lo_dev / hi_dev are device arrays [off[ycnt]].
+ *
+ * Normalisation (on the device, one thread per query): the query's intervals are ordered by (lo, hi); empty ones
+ * (lo > hi) are dropped; each later one is clipped to start above the largest hi before it, or dropped where nothing is
+ * left (nothing follows hi = 0xFFFFFFFF).  The survivors are pairwise disjoint, so no row is offered twice to one query.
+ * annhip_tag_runs_set writes the (start, len) of the normalised intervals, in that order, into the query's slice of
+ * start_dev / len_dev [off[ycnt]] -- lower_bound and upper_bound as annhip_tag_runs finds them -- and (0, 0) for the slots
+ * that the normalisation emptied.  Asynchronous on hip_stream; it stages its offsets in the index's own workspace, so
+ * do not overlap it with a batch that uses that workspace.  Returns 0; -1, with one line on stderr and nothing
+ * launched: without an order, for a NULL array, for offsets that decrease or do not start at 0, for a set of more than 256
+ * intervals.
+ *
+ * Pieces: with split_rows = S > 0 every run is cut at the GLOBAL positions S, 2S, 3S, ... of the order (not at offsets
+ * from its own start), so the queries of one tenant produce identical pieces and overlapping windows aligned ones, whose
+ * fetch the scan shares as before; the pieces of a run go to different workgroups: the set call splits long runs over
+ * the CUs.  Each piece, and with S = 0 each interval slot, is one entry of the scan's list; a per-query merge of the
+ * entries' partial lists writes the output row.
+ * Returns the entry count E >= 0.  With S > 0 E is the number of pieces, which depends on the data: the call
+ * SYNCHRONISES hip_stream once to read it (after the runs are known, before the scan is launched).  With S = 0 the call
+ * does not synchronise: everything goes to hip_stream and E = off[ycnt], one entry per interval slot -- a slot whose
+ * interval is empty, was dropped or matches no row is an entry with an empty run, which fetches nothing.
+ * Returns -2, with one line on stderr and the outputs untouched: in every case in which annhip_query_sorted refuses; for
+ * a NULL off_host, lo_dev or hi_dev; for offsets that decrease or do not start at 0; for a set of more than 256 intervals;
+ * for 0 < S < 64; for E * kq > 2^27 partial slots (with S > 0 this one is known only after the runs have been computed:
+ * those small launches have happened, the scan has not).
+ * With annhip_profile(ix, 1), annhip_stats' out[3] counts the rows fetched into tiles, as for annhip_query_sorted.
+ * Limits: at most 256 intervals per query; one order and one mask per index; no router, no sharded form. */
+int annhip_tag_runs_set(annhip_index *ix, void *hip_stream, size_t ycnt, const uint32_t *off_host /* [ycnt + 1] */,
+                        const uint32_t *lo_dev, const uint32_t *hi_dev /* [off[ycnt]] */, uint32_t *start_dev,
+                        uint32_t *len_dev /* [off[ycnt]] */);
+long annhip_query_sorted_set(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev, int alias,
+                             size_t kq, const ftype *radius_dev /* may be NULL */, const uint32_t *off_host,
+                             const uint32_t *lo_dev, const uint32_t *hi_dev, size_t split_rows, size_t *ids_dev,
+                             ftype *dists_dev, uint32_t *counts_dev /* written iff radius_dev != NULL */);
 
 /* ---- synthetic data of the reference's drivers------------------------------------------------------ */
 /* out[0..count) = iid N(0,1) by Box-Muller on the CALLER's libc random() stream, value for value what genRand /

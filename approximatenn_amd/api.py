@@ -1151,52 +1151,16 @@ class Index:
         import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
-        if isinstance(where, (tuple, list)) and len(where) == 3:
+        if where is not None or k is not None:  # the entries of fixed mode
             kq = self.k if k is None else self._check_k(k)
             if kq < 1:
                 raise ValueError("query(k=...): k must be at least 1")
-            pred = _where_dev(where, Q, y.device)
-            ids = out_ids if out_ids is not None else torch.empty((Q, kq), dtype=torch.int64, device=y.device)
-            dists = out_dists if out_dists is not None else torch.empty((Q, kq), dtype=y.dtype, device=y.device)
-            assert tuple(ids.shape) == (Q, kq) and tuple(dists.shape) == (Q, kq) and ids.is_contiguous() and dists.is_contiguous()
-            rc = self._between(y, alias, kq, None, pred, ids, dists, None, ws, stream)
-            return ids, dists, rc
-        if k is not None:
-            k = self._check_k(k)
-            if k < 1:
-                raise ValueError("query(k=...): k must be at least 1")
-            qm = qv = None
-            if where is not None:
-                qm, qv = _where_dev(where, Q, y.device)
-            ids = out_ids if out_ids is not None else torch.empty((Q, k), dtype=torch.int64, device=y.device)
-            dists = out_dists if out_dists is not None else torch.empty((Q, k), dtype=y.dtype, device=y.device)
-            assert tuple(ids.shape) == (Q, k) and tuple(dists.shape) == (Q, k) and ids.is_contiguous() and dists.is_contiguous()
-            if qm is not None and stream is not None and torch.cuda.current_stream(y.device) != stream:
-                stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate arrays were made on that one
-            rc = self.lib.annhip_query_k(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
-                                         int(alias), k, qm.data_ptr() if qm is not None else None,
-                                         qv.data_ptr() if qv is not None else None, ids.data_ptr(), dists.data_ptr())
-            if rc == -2:
-                raise ValueError("annhip_query_k refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
-                                 % (k, self.max_query_k))
-            if qm is not None and stream is not None:
-                qm.record_stream(stream), qv.record_stream(stream)
-            return ids, dists, rc
-        if where is not None:
-            qm, qv = _where_dev(where, Q, y.device)
-            if not self.has_tags:
+            pred = _where_dev(where, Q, y.device) if where is not None else None
+            if k is None and len(pred) == 2 and not self.has_tags:  # (the other forms leave this to the library)
                 raise ValueError("query(where=...): the index has no tags (Index.set_tags)")
-            ids = out_ids if out_ids is not None else torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
-            dists = out_dists if out_dists is not None else torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
-            if stream is not None and torch.cuda.current_stream(y.device) != stream:
-                stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate arrays were made on that one
-            nex = self.lib.annhip_query_tagged(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
-                                               int(alias), qm.data_ptr(), qv.data_ptr(), ids.data_ptr(), dists.data_ptr())
-            if nex == -2:
-                raise ValueError("annhip_query_tagged refused (fixed mode off, or no tags)")
-            if stream is not None:  # the arrays may be freed once this call returns: keep them until the batch has read them
-                qm.record_stream(stream), qv.record_stream(stream)
-            return ids, dists, nex
+            ids, dists, _, rc = self._fixed_call(self._fixed_entry(pred, k is not None, False), y, alias, kq, None, pred,
+                                                 out_ids, out_dists, ws, stream)
+            return ids, dists, rc
         ids = out_ids if out_ids is not None else torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
         dists = out_dists if out_dists is not None else torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
         if ws is None and stream is None:
@@ -1206,41 +1170,81 @@ class Index:
                                            int(alias), mode, ids.data_ptr(), dists.data_ptr())
         return ids, dists, nex
 
-    def _between(self, y, alias, kq, rad, pred, ids, dists, counts, ws, stream):
-        """annhip_query_between on `stream` / `ws`: the stream and lifetime handling of the pair form's arrays."""
-        import torch
-        if stream is not None and torch.cuda.current_stream(y.device) != stream:
-            stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate (and radius) arrays were made on that one
-        # (a radius call may have no rows: annhip_query_radius wants non-NULL pointers then, as Index.query_radius gives it)
-        hold = torch.empty((1,), dtype=torch.int64, device=y.device) if rad is not None else None
-        rc = self.lib.annhip_query_between(self.h, ws, stream.cuda_stream if stream is not None else None, y.shape[0], y.data_ptr(),
-                                           int(alias), kq, _ptr(rad, hold) if rad is not None else None, pred[0].data_ptr(),
-                                           pred[1].data_ptr(), pred[2].data_ptr(),
-                                           _ptr(ids, hold) if rad is not None else ids.data_ptr(), dists.data_ptr(),
-                                           counts.data_ptr() if counts is not None else None)
-        if rc == -2:
-            raise ValueError("annhip_query_between refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
-                             % (kq, self.max_query_k))
-        if stream is not None:  # keep the arrays until the batch has read them
-            for t in pred + ((rad, ids, dists, counts) if rad is not None else ()):  # as the pair's calls do
-                t.record_stream(stream)
-        return rc
+    # Which C entry a call takes -- the same one for every argument combination as ever -- as (name, the tail of its
+    # ValueError, its arguments after `alias`: made from kq, the radius, the predicate's pointers, (ids, dists), counts).
+    # pred: None, a pair or a triple of arrays; k_given / radius: the call names a k of its own / is a radius call.
+    @staticmethod
+    def _fixed_entry(pred, k_given, radius):
+        refused = "k=%(k)d (fixed mode off, k outside 1..%(kmax)d, no tags, or a resharded index)"
+        if pred is not None and len(pred) == 3:
+            return "annhip_query_between", refused, lambda kq, r, q, o, c: (kq, r) + q + o + (c,)
+        if radius:
+            return "annhip_query_radius", refused, lambda kq, r, q, o, c: (kq, r) + q + o + (c,)
+        if k_given:
+            return "annhip_query_k", refused, lambda kq, r, q, o, c: (kq,) + q + o
+        return "annhip_query_tagged", "(fixed mode off, or no tags)", lambda kq, r, q, o, c: q + o
 
-    def _exact_between(self, y, alias, kq, rad, pred):
-        """annhip_index_exact_query_between -> (ids, dists, counts); counts is written only with a radius."""
+    @staticmethod
+    def _exact_entry(pred, k_given, radius):
+        refused = "k=%(k)d (k outside 1..1024 or larger than the rows on offer, no tags, or a resharded index)"
+        if pred is not None and len(pred) == 3:
+            return "annhip_index_exact_query_between", refused, lambda kq, r, q, o, c: (kq, r) + q + o + (c,)
+        if radius:
+            return "annhip_index_exact_query_radius", refused, lambda kq, r, q, o, c: (kq, r) + q + o + (c,)
+        if k_given:
+            return "annhip_index_exact_query_k", refused, lambda kq, r, q, o, c: (kq,) + q + o
+        if pred is not None:
+            return ("annhip_index_exact_query_tagged", "this index (no tags, resharded, or k larger than the rows on offer)",
+                    lambda kq, r, q, o, c: q + o)
+        return ("annhip_index_exact_query", "this index (resharded, or k larger than the rows on offer)",
+                lambda kq, r, q, o, c: o)
+
+    def _fixed_call(self, entry, y, alias, kq, rad, pred, out_ids, out_dists, ws, stream):
+        """One call of a fixed-mode entry (_fixed_entry) on `stream` / `ws` -> (ids, dists, counts, rc); counts is None
+        without a radius.  The outputs, the order of the two streams, the ValueError of a refusal, and every device tensor
+        of the call kept until `stream` has passed it."""
         import torch
+        name, refused, layout = entry
+        Q = y.shape[0]
+        ids = out_ids if out_ids is not None else torch.empty((Q, kq), dtype=torch.int64, device=y.device)
+        dists = out_dists if out_dists is not None else torch.empty((Q, kq), dtype=y.dtype, device=y.device)
+        assert tuple(ids.shape) == (Q, kq) and tuple(dists.shape) == (Q, kq) and ids.is_contiguous() and dists.is_contiguous()
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device) if rad is not None else None
+        given = tuple(t for t in (pred or ()) + (rad,) if t is not None)
+        if given and stream is not None and torch.cuda.current_stream(y.device) != stream:
+            stream.wait_stream(torch.cuda.current_stream(y.device))  # the predicate, radius and output arrays were made on that one
+        # (a radius call may have no rows: the library wants non-NULL radius and ids pointers then)
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device) if rad is not None else None
+        rc = getattr(self.lib, name)(
+            self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(), int(alias),
+            *layout(kq, _ptr(rad, hold) if rad is not None else None,
+                    tuple(t.data_ptr() for t in pred) if pred is not None else (None, None),
+                    (_ptr(ids, hold) if rad is not None else ids.data_ptr(), dists.data_ptr()),
+                    counts.data_ptr() if counts is not None else None))
+        if rc == -2:
+            raise ValueError("%s refused %s" % (name, refused % {"k": kq, "kmax": self.max_query_k}))
+        if stream is not None:  # the arrays may be freed once this call returns: keep them until the batch has read them
+            for t in (y, ids, dists) + given + tuple(t for t in (counts, hold) if t is not None):
+                t.record_stream(stream)
+        return ids, dists, counts, rc
+
+    def _exact_call(self, entry, y, alias, kq, rad, pred):
+        """One call of an exact entry (_exact_entry), synchronous on the null stream -> (ids, dists, counts); counts is
+        None without a radius.  ValueError where the library refuses."""
+        import torch
+        name, refused, layout = entry
         Q = y.shape[0]
         ids = torch.empty((Q, kq), dtype=torch.int64, device=y.device)
         dists = torch.empty((Q, kq), dtype=y.dtype, device=y.device)
-        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device) if rad is not None else None
         torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
-        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
-        if self.lib.annhip_index_exact_query_between(self.h, Q, y.data_ptr(), int(bool(alias)), kq,
-                                                     _ptr(rad, hold) if rad is not None else None, pred[0].data_ptr(),
-                                                     pred[1].data_ptr(), pred[2].data_ptr(), _ptr(ids, hold), _ptr(dists, hold),
-                                                     counts.data_ptr()) != 0:
-            raise ValueError("annhip_index_exact_query_between refused k=%d (k outside 1..1024 or larger than the rows on "
-                             "offer, no tags, or a resharded index)" % kq)
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)  # (an empty batch: the radius entries refuse NULL arrays)
+        if getattr(self.lib, name)(
+                self.h, Q, y.data_ptr(), int(bool(alias)),
+                *layout(kq, _ptr(rad, hold) if rad is not None else None,
+                        tuple(t.data_ptr() for t in pred) if pred is not None else (None, None),
+                        (_ptr(ids, hold), _ptr(dists, hold)), counts.data_ptr() if counts is not None else None)) != 0:
+            raise ValueError("%s refused %s" % (name, refused % {"k": kq}))
         return ids, dists, counts
 
     def exact_query(self, y, alias=False, where=None, k=None):
@@ -1253,49 +1257,15 @@ class Index:
         [Q,k] tensors; ValueError for a bool or a non-integer and where the library refuses (k outside 1..1024,
         k > n - alias, a resharded index, where= without tags).  where = (qmask, qlo, qhi) as in query():
         annhip_index_exact_query_between, with or without k=."""
-        import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
-        if where is not None and isinstance(where, (tuple, list)) and len(where) == 3:
-            kq = self.k if k is None else self._check_k(k)
-            if kq < 1:
-                raise ValueError("exact_query(k=...): k must be in 1..1024")
-            pred = _where_dev(where, Q, y.device)
-            if not self.has_tags:
-                raise ValueError("exact_query(where=...): the index has no tags (Index.set_tags)")
-            return self._exact_between(y, alias, kq, None, pred)[:2]
-        if k is not None:
-            k = self._check_k(k)
-            if k < 1:
-                raise ValueError("exact_query(k=...): k must be in 1..1024")
-            qm = qv = None
-            if where is not None:
-                qm, qv = _where_dev(where, Q, y.device)
-            ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
-            dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
-            torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
-            if self.lib.annhip_index_exact_query_k(self.h, Q, y.data_ptr(), int(bool(alias)), k,
-                                                   qm.data_ptr() if qm is not None else None,
-                                                   qv.data_ptr() if qv is not None else None, ids.data_ptr(), dists.data_ptr()) != 0:
-                raise ValueError("annhip_index_exact_query_k refused k=%d (k outside 1..1024 or larger than the rows on offer, "
-                                 "no tags, or a resharded index)" % k)
-            return ids, dists
-        if where is not None:
-            qm, qv = _where_dev(where, Q, y.device)
-            if not self.has_tags:
-                raise ValueError("exact_query(where=...): the index has no tags (Index.set_tags)")
-        ids = torch.empty((Q, self.k), dtype=torch.int64, device=y.device)
-        dists = torch.empty((Q, self.k), dtype=y.dtype, device=y.device)
-        if where is not None:
-            torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
-            if self.lib.annhip_index_exact_query_tagged(self.h, Q, y.data_ptr(), int(bool(alias)), qm.data_ptr(), qv.data_ptr(),
-                                                        ids.data_ptr(), dists.data_ptr()) != 0:
-                raise ValueError("annhip_index_exact_query_tagged refused this index (no tags, resharded, or k larger than "
-                                 "the rows on offer)")
-            return ids, dists
-        if self.lib.annhip_index_exact_query(self.h, Q, y.data_ptr(), int(bool(alias)), ids.data_ptr(), dists.data_ptr()) != 0:
-            raise ValueError("annhip_index_exact_query refused this index (resharded, or k larger than the rows on offer)")
-        return ids, dists
+        kq = self.k if k is None else self._check_k(k)
+        if kq < 1:
+            raise ValueError("exact_query(k=...): k must be in 1..1024")
+        pred = _where_dev(where, Q, y.device) if where is not None else None
+        if pred is not None and (k is None or len(pred) == 3) and not self.has_tags:  # (k= with a pair leaves it to the library)
+            raise ValueError("exact_query(where=...): the index has no tags (Index.set_tags)")
+        return self._exact_call(self._exact_entry(pred, k is not None, False), y, alias, kq, None, pred)[:2]
 
     def rerank(self, y, cand, k=None, stream=None, out_ids=None, out_dists=None):
         """annhip_index_rerank: the exact top-k of caller-supplied candidates on the index's NATIVE rows (whatever set_rows
@@ -1354,68 +1324,27 @@ class Index:
         NaN radius matches nothing, +inf gives the row of query(k=k) bit for bit.  where, ws and stream as in query(k=).
         ValueError for a bool or non-integer k, for a radius of wrong shape or dtype, and where the library refuses (fixed
         mode off, k outside 1..max_query_k, where= without tags, a resharded index); nothing is launched then."""
-        import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
         k = self.k if k is None else self._check_k(k)
         if k < 1:
             raise ValueError("query_radius: k must be at least 1")
         rad = _radius_dev(radius, Q, y.dtype, y.device)
-        qm = qv = None
         pred = _where_dev(where, Q, y.device) if where is not None else None
-        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
-        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
-        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
-        if pred is not None and len(pred) == 3:  # (qmask, qlo, qhi): annhip_query_between
-            self._between(y, alias, k, rad, pred, ids, dists, counts, ws, stream)
-            return ids, dists, counts
-        if pred is not None:
-            qm, qv = pred
-        if stream is not None and torch.cuda.current_stream(y.device) != stream:
-            stream.wait_stream(torch.cuda.current_stream(y.device))  # the radius, predicate and output arrays were made on that one
-        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
-        rc = self.lib.annhip_query_radius(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
-                                          int(alias), k, _ptr(rad, hold), qm.data_ptr() if qm is not None else None,
-                                          qv.data_ptr() if qv is not None else None, _ptr(ids, hold), dists.data_ptr(),
-                                          counts.data_ptr())
-        if rc == -2:
-            raise ValueError("annhip_query_radius refused k=%d (fixed mode off, k outside 1..%d, no tags, or a resharded index)"
-                             % (k, self.max_query_k))
-        if stream is not None:  # keep the arrays until the batch has read them
-            for t in (rad, qm, qv, ids, dists, counts):
-                if t is not None:
-                    t.record_stream(stream)
-        return ids, dists, counts
+        return self._fixed_call(self._fixed_entry(pred, True, True), y, alias, k, rad, pred, None, None, ws, stream)[:3]
 
     def exact_query_radius(self, y, radius, k, alias=False, where=None):
         """annhip_index_exact_query_radius: the ground truth of query_radius -- exact_query(k=k) cut at the radius ->
         (ids int64 [Q,k], sq dists [Q,k], counts int32 [Q]), padded with (n_total, +inf).  radius and where as in
         query_radius.  ValueError as exact_query(k=) raises it, and for a radius of wrong shape or dtype."""
-        import torch
         assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
         Q = y.shape[0]
         k = self._check_k(k)
         if k < 1:
             raise ValueError("exact_query_radius: k must be in 1..1024")
         rad = _radius_dev(radius, Q, y.dtype, y.device)
-        qm = qv = None
-        if where is not None:
-            pred = _where_dev(where, Q, y.device)
-            if len(pred) == 3:  # (qmask, qlo, qhi): annhip_index_exact_query_between
-                return self._exact_between(y, alias, k, rad, pred)
-            qm, qv = pred
-        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
-        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
-        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
-        torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
-        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
-        if self.lib.annhip_index_exact_query_radius(self.h, Q, y.data_ptr(), int(bool(alias)), k, _ptr(rad, hold),
-                                                    qm.data_ptr() if qm is not None else None,
-                                                    qv.data_ptr() if qv is not None else None, _ptr(ids, hold),
-                                                    _ptr(dists, hold), counts.data_ptr()) != 0:
-            raise ValueError("annhip_index_exact_query_radius refused k=%d (k outside 1..1024 or larger than the rows on "
-                             "offer, no tags, or a resharded index)" % k)
-        return ids, dists, counts
+        pred = _where_dev(where, Q, y.device) if where is not None else None
+        return self._exact_call(self._exact_entry(pred, True, True), y, alias, k, rad, pred)
 
     def host_stream(self, max_ycnt, lanes=3):
         """annhip_stream_open: pipeline for host-resident (numpy) batches; see HostStream."""

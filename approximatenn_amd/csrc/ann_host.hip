@@ -1741,36 +1741,40 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
 static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *radius, size_t *ids, FT *dists, u32 *counts,
                                hipStream_t s);
 
-// How a fixed-mode call ends once stage 2 has written its rows of k: the appended rows merged into them ("stage2_network"
-// of annhip_stage_ms) -- the hashed ones through the buckets this call probes, the rest scanned exactly --, the trim of a
-// radius call (radius != NULL), the closing marks and the index's counters.  pbits: NULL where the call does not probe.
-static void fixed_mode_tail(annhip_index *ix, std::vector<hipEvent_t> *marks, hipStream_t s, size_t Q, const FT *y, int alias,
-                            size_t k, const TagQuery *tq, const u32 *codes, const unsigned char *pbits, size_t *ids_dev, FT *out_d,
-                            const FT *radius, u32 *counts_dev) {
-  unsigned long long *scored = ix->profile == 1 ? ix->d_rows + 8 : NULL;
-  if (ix->tail_mh) launch_tail_hash_merge(ix, Q, y, k, tq, codes, pbits, pbits ? ix->probe : 0, ids_dev, out_d, scored, s);
-  if (ix->tail_m > ix->tail_mh) launch_tail_merge(ix, Q, y, alias, k, tq, k, ids_dev, out_d, ids_dev, out_d, scored, s, ix->tail_mh);
-  // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
-  // so the trim is in neither the stage-1 nor the stage-2 figure)
-  if (radius) launch_radius_trim(Q, k, n_total(ix), radius, ids_dev, out_d, counts_dev, s);
-  seg_mark(ix, marks, s);
-  seg_mark(ix, marks, s);
+// How a call of the query path ends: the marks padded to the seven that annhip_stats reads (a path with fewer stages
+// leaves its last segments at zero) and handed over, and the index's counter.
+static void finish_call(annhip_index *ix, std::vector<hipEvent_t> *marks, hipStream_t s, size_t Q) {
+  while (marks && marks->size() < 7) seg_mark(ix, marks, s);
   if (marks) ix->seg_used.push_back(*marks);
   ix->queries += (double)Q;
 }
+
+// What the entries of fixed mode ask of fixed_query (defined below the stage 2 of a per-call k).
+struct FixedCall {
+  size_t kq;           // the k of the call: sizes K1 and every buffer
+  bool stage2_kq;      // false: kq == ix->k and the index's own selection path; true: stage2_kq_kernel, whatever kq is
+  const TagQuery *tq;  // the tag family of stage 1 and stage 2, or NULL
+  const FT *radius;    // annhip_query_radius / _between: stage1_radius_kernel and the trim with counts; stage2_kq only
+  u32 *counts;
+};
+static long fixed_query(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
+                        const FixedCall &c, size_t *ids_dev, ftype *dists_dev, int codes_ready = 0);
 
 // ----------------------------------------------------------------------------- query
 // codes_ready: ws.codes already holds the hash codes of this batch (query_gpu computes them chunk by chunk while the
 // batch is still arriving over PCIe)
 // codes_ext / qstride: the batch is a SLICE of a larger one whose codes (try-major reads, stride qstride) the caller holds:
 // codes_ext points at the slice's first query (annhip_query_slice).
+// An index in fixed mode goes to fixed_query with its own k: what follows is the parity path.
 static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
                        int mode, size_t *ids_dev, ftype *dists_dev, int codes_ready = 0, const u32 *codes_ext = NULL,
-                       size_t qstride = 0, const TagQuery *tq = NULL) {
+                       size_t qstride = 0) {
   // codes_ready: 1 = ws.codes holds the batch's codes, 2 = and ws.d_fcount has been reset
-  // tq: annhip_query_tagged (fixed mode only, checked there): the tag family of stage 1 and stage 2
+  if (ix->fixed && !codes_ext)
+    return fixed_query(ix, ws, s, Q, y_dev, alias, FixedCall{ix->k, false, NULL, NULL, NULL}, ids_dev, dists_dev, codes_ready);
   if (!Q) return 0;
   if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
+  if (ix->fixed) die("annhip_query_slice: not available in fixed mode");
   const QParams P = query_params(ix);
   if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
   const FT *y = reinterpret_cast<const FT *>(y_dev);
@@ -1781,53 +1785,19 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
   seg_mark(ix, marks, s);
   const u32 *codes = codes_ext;
   bool fcount_zeroed = codes_ready == 2;
-  const bool probing = ix->fixed && ix->probe > 0;  // parity-mode queries ignore the probe setting
-  unsigned char *pbits = NULL;
-  if (!codes_ext) {
+  if (!codes_ext) {  // (parity-mode queries ignore the probe setting)
     u32 *own = (u32 *)ws.codes.need(sizeof(u32) * Q * P.T);
-    if (probing) {  // fixed mode with pair bits: the hash kernel that also ranks the projections
-      pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
-      launch_codes_probe(P, Q, y, own, pbits, ix->probe, s, ws.d_fcount);
-      fcount_zeroed = true;
-    } else if (!codes_ready) {
+    if (!codes_ready) {
       launch_codes(P, codes_needed(ix, Q), y, own, s, ws.d_fcount);  // also resets the batch's flagged-query counter
       fcount_zeroed = codes_needed(ix, Q) > 0;
     }
     codes = own;
-  } else if (ix->fixed) {
-    die("annhip_query_slice: not available in fixed mode");
   }
   seg_mark(ix, marks, s);
   u32 *top_i = (u32 *)ws.top_i.need(sizeof(u32) * Q * k);
   FT *top_d = (FT *)ws.top_d.need(sizeof(FT) * Q * k);
   FT *cand_d = NULL;
   u32 *cand_i = NULL, *nvt = NULL;
-  // ---- fixed mode (opt-in, NOT the reference's results): query x hashes into ITS OWN buckets (the
-  // reference reads code[i*Q+x] of a [Q][T] array, Q2), all L1 / L2 slots are candidates (the reference orders the
-  // first 2^floor(log2 L) only, Q1), and the answer is simply the k smallest distinct (distance, id) keys -- stage 1's
-  // selection kernel, finalize1 without its proof, stage 2 by selection.  Single device, whole index.
-  if (ix->fixed) {
-    if (!(ix->lo == 0 && ix->hi == ix->n)) die("fixed mode needs the whole index on this device");
-    cand_d = (FT *)ws.cand_d.need(sizeof(FT) * Q * K1);
-    cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
-    nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
-    u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-    if (ix->filter || tq || probing)  // one kernel family each, for every pair-bit setting (b = 0: no ranked bits)
-      launch_stage1_fixed(ix, P, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, NULL, cand_d, cand_i, nvt, nvo, s);
-    else launch_stage1(ix, P, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
-    seg_mark(ix, marks, s);
-    hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, P.k, K1, P.L1, P.P1,
-                       cand_d, cand_i, nvt, top_i, top_d, k, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
-    HIPCHECK(hipGetLastError());
-    seg_mark(ix, marks, s);
-    FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * k);
-    if (!stage2_select_with_fallback(P, Q, y, alias, 0, Q, top_i, top_d, NULL, ids_dev, out_d, ws.flist, ws.d_fcount, ws.r2i,
-                                     ws.r2d, NULL, ix->profile == 1 ? ix->d_rows + 8 : NULL, s, ix->filter, tq))
-      die("fixed mode: stage-2 shape not supported");
-    seg_mark(ix, marks, s);
-    fixed_mode_tail(ix, marks, s, Q, y, alias, (size_t)k, tq, codes, pbits, ids_dev, out_d, NULL, NULL);
-    return 0;
-  }
   // pruned stage 1 (annhip_index_set_prune): preselect on the narrow copy, rescore on native rows -- the same answers
 #ifdef USE_FLOAT
   const bool pruned = mode == 0 && !codes_ext && prune_active(ix) && K1 <= 32 && ix->prune_kp >= K1;
@@ -1865,9 +1835,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
       seg_mark(ix, marks, s);
       launch_exact_select(P.L2, P.Lc2, P.Lc2, k, Q, r2i, r2d, fl, 0, NULL, out_d, k, 0, s, ws.d_fcount, ids_dev);
       seg_mark(ix, marks, s);
-      seg_mark(ix, marks, s);
-      if (marks) ix->seg_used.push_back(marks_store);
-      ix->queries += (double)Q;
+      finish_call(ix, marks, s, Q);
       return -1;
     }
   }
@@ -1925,10 +1893,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
     // one kernel: row assembly, neighbour gathers, network and size_t ids per query (stage2_fused_kernel)
     launch_stage2_fused<size_t>(P, Q, y, alias, 0, Q, top_i, top_d, ids_dev, out_d, rows_ctr, s);
     seg_mark(ix, marks, s);  // "stage2_rows" = the whole fused stage 2; "stage2_network" and "widen" stay 0
-    seg_mark(ix, marks, s);
-    seg_mark(ix, marks, s);
-    if (marks) ix->seg_used.push_back(marks_store);
-    ix->queries += (double)Q;
+    finish_call(ix, marks, s, Q);
     return nflag;
   }
   if (ix->lo == 0 && ix->hi == ix->n && env().tail != 0 &&
@@ -1936,10 +1901,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
                                   ws.r2d, ix->d_rows + 2, rows_ctr, s)) {
     // long stage-2 rows (k >= 32): selection + proof instead of the P2-entry network; "stage2_rows" = all of it
     seg_mark(ix, marks, s);
-    seg_mark(ix, marks, s);
-    seg_mark(ix, marks, s);
-    if (marks) ix->seg_used.push_back(marks_store);
-    ix->queries += (double)Q;
+    finish_call(ix, marks, s, Q);
     return nflag;
   }
   u32 *out_i = (u32 *)ws.out_i.need(sizeof(u32) * Q * k);
@@ -1958,8 +1920,7 @@ static long query_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, si
   widen_ids_kernel<<<grid_for(Q * k, 256, 1u << 30), 256, 0, s>>>(Q * k, out_i, ids_dev);
   HIPCHECK(hipGetLastError());
   seg_mark(ix, marks, s);
-  if (marks) ix->seg_used.push_back(marks_store);
-  ix->queries += (double)Q;
+  finish_call(ix, marks, s, Q);
   return nflag;
 }
 
@@ -1995,19 +1956,34 @@ extern "C" long annhip_query_on(annhip_index *ix, annhip_workspace *ws, void *hi
   return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, mode, ids_dev, dists_dev);
 }
 
+// ----------------------------------------------------------------------------- the entries of fixed mode with their refusals
+// What annhip_query_tagged / _k / _radius / _between refuse: fixed mode off; then, for all but annhip_query_tagged
+// (resharded = false: it goes on to fixed_query's abort there, as it always did), a resharded index; then the entry's
+// own reasons in its order, each its text or NULL.  Prints "who: why" for the first that holds and returns it, or NULL.
+static const char *const NO_TAGS = "the index has no tags (annhip_index_set_tags)";
+static const char *pair_or_neither(const uint32_t *qmask_dev, const uint32_t *qvalue_dev) {
+  return (qmask_dev != NULL) != (qvalue_dev != NULL) ? "qmask_dev and qvalue_dev must both be given, or neither" : NULL;
+}
+static const char *fixed_refusal(const annhip_index *ix, const char *who, bool resharded, std::initializer_list<const char *> own) {
+  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
+                    : resharded && !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
+                                                                     : NULL;
+  for (const char *w : own)
+    if (!why) why = w;
+  if (why) fprintf(stderr, "%s: %s\n", who, why);
+  return why;
+}
+
 // Contract: include/ann_hip.h.  A refusal launches nothing and leaves the outputs untouched.
 extern "C" long annhip_query_tagged(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t Q, const ftype *y_dev,
                                     int alias, const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
                                     ftype *dists_dev) {
-  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
-                    : !ix->tags ? "the index has no tags (annhip_index_set_tags)"
-                    : !qmask_dev || !qvalue_dev ? "qmask_dev and qvalue_dev must both be given" : NULL;
-  if (why) {
-    fprintf(stderr, "annhip_query_tagged: %s\n", why);
+  if (fixed_refusal(ix, "annhip_query_tagged", false,
+                    {!ix->tags ? NO_TAGS : NULL, !qmask_dev || !qvalue_dev ? "qmask_dev and qvalue_dev must both be given" : NULL}))
     return -2;
-  }
   const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
-  return query_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
+  return fixed_query(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, Q, y_dev, alias, FixedCall{ix->k, false, &tq, NULL, NULL},
+                     ids_dev, dists_dev);
 }
 
 // ----------------------------------------------------------------------------- query with a per-call k (annhip_query_k)
@@ -2068,17 +2044,26 @@ static void launch_stage2_kq(const QParams &P, size_t Q, const FT *y, int alias,
   HIPCHECK(hipGetLastError());
 }
 
-// query_impl's fixed branch with kq in the place of k (the caller has validated everything).  radius != NULL
-// (annhip_query_radius, kq = its kcap): stage1_radius_kernel in stage 1, and the trim with counts_dev at the end.
-static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias, size_t kq,
-                         const TagQuery *tq, const FT *radius, size_t *ids_dev, ftype *dists_dev, u32 *counts_dev) {
+// ----------------------------------------------------------------------------- fixed mode (annhip_index_set_fixed)
+// Opt-in, NOT the reference's results: query x hashes into ITS OWN buckets (the reference reads
+// code[i*Q+x] of a [Q][T] array, Q2), all L1 / L2 slots are candidates (the reference orders the first 2^floor(log2 L)
+// only, Q1), and the answer is simply the kq smallest distinct (distance, id) keys -- stage 1's selection kernel,
+// finalize1 without its proof, stage 2 by selection.  Single device, whole index.  The one path of every fixed-mode call:
+// hash (with pair bits: the kernel that also ranks the projections), stage 1, finalize1, the stage 2 that c names, the
+// appended rows, a radius call's trim.  The entries have refused what can be refused.
+// codes_ready (query_gpu): 1 = ws.codes holds the batch's codes, 2 = and ws.d_fcount has been reset; a probing call
+// hashes again all the same, for the ranked bits.
+static long fixed_query(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
+                        const FixedCall &c, size_t *ids_dev, ftype *dists_dev, int codes_ready) {
   if (!Q) return 0;
   if (Q >= 0x7FFFFFFFull / (size_t)(ix->T > 0 ? ix->T : 1)) die("query batch too large");
+  if (!(ix->lo == 0 && ix->hi == ix->n)) die("fixed mode needs the whole index on this device");
   const QParams P = query_params(ix);
   QParams P1 = P;  // stage 1's view: k = kq
-  P1.k = (int)kq;
+  P1.k = (int)c.kq;
   if (!ws.d_fcount) ws.d_fcount = dev_alloc<u32>(4);
   const FT *y = reinterpret_cast<const FT *>(y_dev);
+  const size_t kq = c.kq;
   const int K1 = (int)kq + 1;
   std::vector<hipEvent_t> marks_store, *marks = ix->profile == 1 ? &marks_store : NULL;
   seg_mark(ix, marks, s);
@@ -2088,7 +2073,7 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   if (probing) {
     pbits = (unsigned char *)ws.pbits.need((size_t)Q * P.T * ix->probe);
     launch_codes_probe(P, Q, y, codes, pbits, ix->probe, s, ws.d_fcount);
-  } else {
+  } else if (!codes_ready) {
     launch_codes(P, Q, y, codes, s, ws.d_fcount);
   }
   seg_mark(ix, marks, s);
@@ -2098,8 +2083,9 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   u32 *cand_i = (u32 *)ws.cand_i.need(sizeof(u32) * Q * K1);
   u32 *nvt = (u32 *)ws.nvt.need(sizeof(u32) * Q);
   u32 *nvo = (u32 *)ws.nvo.need(sizeof(u32) * Q);
-  if (radius || ix->filter || tq || probing)
-    launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, tq, radius, cand_d, cand_i, nvt, nvo, s);
+  if (c.radius || ix->filter || c.tq || probing)  // one kernel family each, for every pair-bit setting (b = 0: no ranked bits)
+    launch_stage1_fixed(ix, P1, Q, y, alias, codes, pbits, probing ? ix->probe : 0, ix->filter, c.tq, c.radius, cand_d, cand_i, nvt,
+                        nvo, s);
   else launch_stage1(ix, P1, Q, y, alias, codes, cand_d, cand_i, nvt, nvo, s, ix->h_tries, ix->use_seg);
   seg_mark(ix, marks, s);
   hipLaunchKernelGGL(finalize1_kernel, dim3(grid_for(Q, 256, 1u << 30)), dim3(256), 0, s, (int)Q, (int)kq, K1, P.L1, P.P1, cand_d,
@@ -2107,9 +2093,23 @@ static long query_k_impl(annhip_index *ix, annhip_workspace &ws, hipStream_t s, 
   HIPCHECK(hipGetLastError());
   seg_mark(ix, marks, s);
   FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
-  launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, tq, ids_dev, out_d, ix->profile == 1 ? ix->d_rows + 8 : NULL, s);
+  unsigned long long *scored = ix->profile == 1 ? ix->d_rows + 8 : NULL;
+  // two stage 2s, different kernels: a call with the index's own k keeps its selection path, annhip_query_k and the
+  // radius calls keep stage2_kq_kernel even where kq == ix->k
+  if (c.stage2_kq) launch_stage2_kq(P, Q, y, alias, top_i, top_d, kq, ix->filter, c.tq, ids_dev, out_d, scored, s);
+  else if (!stage2_select_with_fallback(P, Q, y, alias, 0, Q, top_i, top_d, NULL, ids_dev, out_d, ws.flist, ws.d_fcount, ws.r2i,
+                                        ws.r2d, NULL, scored, s, ix->filter, c.tq))
+    die("fixed mode: stage-2 shape not supported");
   seg_mark(ix, marks, s);
-  fixed_mode_tail(ix, marks, s, Q, y, alias, kq, tq, codes, pbits, ids_dev, out_d, radius, counts_dev);
+  // the appended rows merged into stage 2's rows of kq ("stage2_network" of annhip_stage_ms): the hashed ones through the
+  // buckets this call probes, the rest scanned exactly
+  if (ix->tail_mh) launch_tail_hash_merge(ix, Q, y, kq, c.tq, codes, pbits, probing ? ix->probe : 0, ids_dev, out_d, scored, s);
+  if (ix->tail_m > ix->tail_mh)
+    launch_tail_merge(ix, Q, y, alias, kq, c.tq, kq, ids_dev, out_d, ids_dev, out_d, scored, s, ix->tail_mh);
+  // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
+  // so the trim is in neither the stage-1 nor the stage-2 figure)
+  if (c.radius) launch_radius_trim(Q, kq, n_total(ix), c.radius, ids_dev, out_d, c.counts, s);
+  finish_call(ix, marks, s, Q);
   return 0;
 }
 
@@ -2119,18 +2119,13 @@ extern "C" long annhip_query_k(annhip_index *ix, annhip_workspace *ws, void *hip
                                size_t kq, const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
                                ftype *dists_dev) {
   const bool tagged = qmask_dev && qvalue_dev;
-  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
-                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
-                    : (qmask_dev != NULL) != (qvalue_dev != NULL) ? "qmask_dev and qvalue_dev must both be given, or neither"
-                    : tagged && !ix->tags ? "the index has no tags (annhip_index_set_tags)"
-                    : !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL;
-  if (why) {
-    fprintf(stderr, "annhip_query_k: %s\n", why);
+  if (fixed_refusal(ix, "annhip_query_k", true,
+                    {pair_or_neither(qmask_dev, qvalue_dev), tagged && !ix->tags ? NO_TAGS : NULL,
+                     !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL}))
     return -2;
-  }
   const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
-  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, tagged ? &tq : NULL, NULL, ids_dev,
-                      dists_dev, NULL);
+  return fixed_query(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias,
+                     FixedCall{kq, true, tagged ? &tq : NULL, NULL, NULL}, ids_dev, dists_dev);
 }
 
 // ----------------------------------------------------------------------------- radius queries (annhip_query_radius)
@@ -2149,20 +2144,15 @@ extern "C" long annhip_query_radius(annhip_index *ix, annhip_workspace *ws, void
                                     int alias, size_t kcap, const ftype *radius_dev, const uint32_t *qmask_dev,
                                     const uint32_t *qvalue_dev, size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
   const bool tagged = qmask_dev && qvalue_dev;
-  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
-                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
-                    : !radius_dev ? "radius_dev must be given"
-                    : !ids_dev ? "ids_dev must be given"
-                    : (qmask_dev != NULL) != (qvalue_dev != NULL) ? "qmask_dev and qvalue_dev must both be given, or neither"
-                    : tagged && !ix->tags ? "the index has no tags (annhip_index_set_tags)"
-                    : !query_k_fits(make_params(ix), kcap) ? "kcap outside 1..annhip_index_max_query_k" : NULL;
-  if (why) {
-    fprintf(stderr, "annhip_query_radius: %s\n", why);
+  if (fixed_refusal(ix, "annhip_query_radius", true,
+                    {!radius_dev ? "radius_dev must be given" : NULL, !ids_dev ? "ids_dev must be given" : NULL,
+                     pair_or_neither(qmask_dev, qvalue_dev), tagged && !ix->tags ? NO_TAGS : NULL,
+                     !query_k_fits(make_params(ix), kcap) ? "kcap outside 1..annhip_index_max_query_k" : NULL}))
     return -2;
-  }
   const TagQuery tq = tag_pair(ix->tags, qmask_dev, qvalue_dev);
-  return query_k_impl(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias, kcap, tagged ? &tq : NULL,
-                      reinterpret_cast<const FT *>(radius_dev), ids_dev, dists_dev, counts_dev);
+  return fixed_query(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias,
+                     FixedCall{kcap, true, tagged ? &tq : NULL, reinterpret_cast<const FT *>(radius_dev), counts_dev}, ids_dev,
+                     dists_dev);
 }
 
 // Contract: include/ann_hip.h.  The range form of annhip_query_k (radius_dev == NULL) and annhip_query_radius: the same
@@ -2172,22 +2162,15 @@ extern "C" long annhip_query_between(annhip_index *ix, annhip_workspace *ws, voi
                                      int alias, size_t kq, const ftype *radius_dev, const uint32_t *qmask_dev,
                                      const uint32_t *qlo_dev, const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev,
                                      uint32_t *counts_dev) {
-  const bool own_k = !radius_dev && kq == (size_t)ix->k;
-  const char *why = !ix->fixed ? "fixed mode is off (annhip_index_set_fixed)"
-                    : !(ix->lo == 0 && ix->hi == ix->n) ? "the index does not hold rows [0, n) on this device (resharded)"
-                    : !qmask_dev || !qlo_dev || !qhi_dev ? "qmask_dev, qlo_dev and qhi_dev must all be given"
-                    : !ix->tags ? "the index has no tags (annhip_index_set_tags)"
-                    : radius_dev && !ids_dev ? "ids_dev must be given"
-                    : !own_k && !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL;
-  if (why) {
-    fprintf(stderr, "annhip_query_between: %s\n", why);
+  const bool own_k = !radius_dev && kq == ix->k;
+  if (fixed_refusal(ix, "annhip_query_between", true,
+                    {!qmask_dev || !qlo_dev || !qhi_dev ? "qmask_dev, qlo_dev and qhi_dev must all be given" : NULL,
+                     !ix->tags ? NO_TAGS : NULL, radius_dev && !ids_dev ? "ids_dev must be given" : NULL,
+                     !own_k && !query_k_fits(make_params(ix), kq) ? "kq outside 1..annhip_index_max_query_k" : NULL}))
     return -2;
-  }
   const TagQuery tq{ix->tags, qmask_dev, qlo_dev, qhi_dev};
-  annhip_workspace &w = ws ? *ws : ix->ws;
-  if (own_k) return query_impl(ix, w, (hipStream_t)hip_stream, ycnt, y_dev, alias, 0, ids_dev, dists_dev, 0, NULL, 0, &tq);
-  return query_k_impl(ix, w, (hipStream_t)hip_stream, ycnt, y_dev, alias, kq, &tq, reinterpret_cast<const FT *>(radius_dev), ids_dev,
-                      dists_dev, counts_dev);
+  return fixed_query(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias,
+                     FixedCall{kq, !own_k, &tq, reinterpret_cast<const FT *>(radius_dev), counts_dev}, ids_dev, dists_dev);
 }
 
 extern "C" int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const ftype *radius_dev, size_t *ids_dev,
@@ -3013,12 +2996,23 @@ extern "C" int annhip_index_hash_tail(annhip_index *ix) {
   return 0;
 }
 
-// The three exact scans of an index: over the built rows as before, then -- where rows have been appended -- the tail's
-// scan merged in.  kq = the k of the call.  qmask_dev == NULL: untagged; the pair form passes its value array for both bounds.
+// What the annhip_index_exact_query* entries refuse before they scan, in their order: a resharded index; then the entry's
+// own test of its pointers (args: its text or NULL) and, for a tagged call, an index without tags -- the other way round
+// for annhip_index_exact_query_tagged (tags_first).
+static int index_exact_refusal(const annhip_index *ix, const char *args, bool tagged, bool tags_first = false) {
+  const char *no_tags = tagged && !ix->tags ? NO_TAGS : NULL;
+  const char *why = ix->lo != 0 || ix->hi != ix->n ? "the index does not hold rows [0, n) (resharded)"
+                    : tags_first && no_tags        ? no_tags
+                    : args                         ? args
+                                                   : no_tags;
+  return why ? exact_refuse(why) : 0;
+}
+
+// The three exact scans of an index (its entries have refused what index_exact_refusal names): over the built rows as
+// before, then -- where rows have been appended -- the tail's scan merged in.  kq = the k of the call.  qmask_dev == NULL:
+// untagged; the pair form passes its value array for both bounds.
 static int index_exact(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq, const uint32_t *qmask_dev,
                        const uint32_t *qlo_dev, const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  if (qmask_dev && !ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
   const ftype *pts = reinterpret_cast<const ftype *>(ix->d_points);
   auto built = [&](size_t k, size_t *ids, ftype *dists) {
     if (!qmask_dev) return annhip_exact_knn_filtered(ix->n, ix->d, k, pts, ycnt, y_dev, alias, ix->filter, ids, dists);
@@ -3051,15 +3045,15 @@ static int index_exact(annhip_index *ix, size_t ycnt, const ftype *y_dev, int al
 
 extern "C" int annhip_index_exact_query(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t *ids_dev,
                                         ftype *dists_dev) {
+  if (const int rc = index_exact_refusal(ix, NULL, false)) return rc;
   return index_exact(ix, ycnt, y_dev, alias, ix->k, NULL, NULL, NULL, ids_dev, dists_dev);
 }
 
 extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
                                                const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
                                                ftype *dists_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  if (!ix->tags) return exact_refuse("the index has no tags (annhip_index_set_tags)");
-  if (!qmask_dev || !qvalue_dev) return exact_refuse("tags_dev, qmask_dev and qvalue_dev must all be given");
+  const char *args = !qmask_dev || !qvalue_dev ? "tags_dev, qmask_dev and qvalue_dev must all be given" : NULL;
+  if (const int rc = index_exact_refusal(ix, args, true, true)) return rc;
   return index_exact(ix, ycnt, y_dev, alias, ix->k, qmask_dev, qvalue_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
@@ -3067,24 +3061,29 @@ extern "C" int annhip_index_exact_query_tagged(annhip_index *ix, size_t ycnt, co
 extern "C" int annhip_index_exact_query_k(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kq,
                                           const uint32_t *qmask_dev, const uint32_t *qvalue_dev, size_t *ids_dev,
                                           ftype *dists_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
+  if (const int rc = index_exact_refusal(ix, pair_or_neither(qmask_dev, qvalue_dev), qmask_dev != NULL)) return rc;
   return index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qvalue_dev, qvalue_dev, ids_dev, dists_dev);
 }
 
-// Contract: include/ann_hip.h.  annhip_index_exact_query_k's path, then the trim (ann_radius_kernels.h): the ground truth of
-// annhip_query_radius.  Synchronous, on the null stream.
-extern "C" int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kcap,
-                                               const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qvalue_dev,
-                                               size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  if ((qmask_dev != NULL) != (qvalue_dev != NULL)) return exact_refuse("qmask_dev and qvalue_dev must both be given, or neither");
-  if (!radius_dev || !ids_dev || !dists_dev) return exact_refuse("radius_dev, ids_dev and dists_dev must all be given");
-  if (const int rc = annhip_index_exact_query_k(ix, ycnt, y_dev, alias, kcap, qmask_dev, qvalue_dev, ids_dev, dists_dev)) return rc;
+// The end of the exact radius calls: the rows cut at the radius (ann_radius_kernels.h), then the null stream drained.
+static int exact_trim(const annhip_index *ix, size_t ycnt, size_t kcap, const ftype *radius_dev, size_t *ids_dev, ftype *dists_dev,
+                      uint32_t *counts_dev) {
   launch_radius_trim(ycnt, kcap, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
                      counts_dev, 0);
   HIPCHECK(hipStreamSynchronize(0));
   return 0;
+}
+
+// Contract: include/ann_hip.h.  annhip_index_exact_query_k's path, then the trim: the ground truth of annhip_query_radius.
+// Synchronous, on the null stream.
+extern "C" int annhip_index_exact_query_radius(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t kcap,
+                                               const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qvalue_dev,
+                                               size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev) {
+  const char *args = pair_or_neither(qmask_dev, qvalue_dev);
+  if (!args && (!radius_dev || !ids_dev || !dists_dev)) args = "radius_dev, ids_dev and dists_dev must all be given";
+  if (const int rc = index_exact_refusal(ix, args, qmask_dev != NULL)) return rc;
+  if (const int rc = index_exact(ix, ycnt, y_dev, alias, kcap, qmask_dev, qvalue_dev, qvalue_dev, ids_dev, dists_dev)) return rc;
+  return exact_trim(ix, ycnt, kcap, radius_dev, ids_dev, dists_dev, counts_dev);
 }
 
 // Contract: include/ann_hip.h.  annhip_index_exact_query_k's scans under the range predicate, then -- with a radius --
@@ -3093,15 +3092,12 @@ extern "C" int annhip_index_exact_query_between(annhip_index *ix, size_t ycnt, c
                                                 const ftype *radius_dev, const uint32_t *qmask_dev, const uint32_t *qlo_dev,
                                                 const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev,
                                                 uint32_t *counts_dev) {
-  if (ix->lo != 0 || ix->hi != ix->n) return exact_refuse("the index does not hold rows [0, n) (resharded)");
-  if (!qmask_dev || !qlo_dev || !qhi_dev) return exact_refuse("qmask_dev, qlo_dev and qhi_dev must all be given");
-  if (radius_dev && (!ids_dev || !dists_dev)) return exact_refuse("radius_dev needs ids_dev and dists_dev");
+  const char *args = !qmask_dev || !qlo_dev || !qhi_dev       ? "qmask_dev, qlo_dev and qhi_dev must all be given"
+                     : radius_dev && (!ids_dev || !dists_dev) ? "radius_dev needs ids_dev and dists_dev"
+                                                              : NULL;
+  if (const int rc = index_exact_refusal(ix, args, true)) return rc;
   if (const int rc = index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qlo_dev, qhi_dev, ids_dev, dists_dev)) return rc;
-  if (!radius_dev) return 0;
-  launch_radius_trim(ycnt, kq, n_total(ix), reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
-                     counts_dev, 0);
-  HIPCHECK(hipStreamSynchronize(0));
-  return 0;
+  return radius_dev ? exact_trim(ix, ycnt, kq, radius_dev, ids_dev, dists_dev, counts_dev) : 0;
 }
 
 // ----------------------------------------------------------------------------- the sorted scan (annhip_query_sorted)

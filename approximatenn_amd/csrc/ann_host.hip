@@ -85,7 +85,6 @@ struct EnvCfg {
   int s2_threads = 64;  // ANN_HIP_S2_THREADS: workgroup size of the fused stage-2 kernel (64, or 128; cfg3: 64-66 vs 67-68 us)
   int segx = -1;      // ANN_HIP_SEGX: -1 unset (auto: shards of <= 30 % of the rows), 0 never, 1 whenever the shard qualifies
   size_t lds_row_max = 150 * 1024, exact_bytes = (size_t)1 << 30;
-  size_t exact_rows = 0;  // ANN_HIP_EXACT_ROWS: rows of the device-driven exact workspace (0 = auto)
   int cache_mode = 0;  // ANN_HIP_CACHE: 0 sampled fingerprint (default), 1 strict (full content hash), 2 off
   size_t bk_group = 0;  // ANN_HIP_BK_GROUP: cap on the members per pass of precomp's bucket kernel (0 = what fits the LDS)
   int fin_tail = 1;     // ANN_HIP_FIN_TAIL: 0 = finalize1 as its own launch after stage 1 (A/B; default: in the stage-1 workgroups' tail)
@@ -123,7 +122,6 @@ static void load_env() {
   c.s2_threads = env_int("ANN_HIP_S2_THREADS", 64) == 128 ? 128 : 64;
   c.lds_row_max = env_size("ANN_HIP_LDS_ROW_MAX", 150 * 1024);
   c.exact_bytes = env_size("ANN_HIP_EXACT_BYTES", (size_t)1 << 30);
-  c.exact_rows = env_size("ANN_HIP_EXACT_ROWS", 0);
   c.bk_group = env_size("ANN_HIP_BK_GROUP", 0);
   c.tie = env_int("ANN_HIP_TIE", 1);
   c.codes_lpq = env_int("ANN_HIP_CODES_LPQ", 1);

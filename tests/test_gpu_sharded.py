@@ -70,11 +70,14 @@ class ThreadDist:
 LAST_TIE_QUERIES = {}
 
 
-def _run_sharded(prec, save_arrays, pts, y, world, alias=False, fast=True, pipelined=False, schedule=None):
+def _run_sharded(prec, save_arrays, pts, y, world, alias=False, fast=True, pipelined=False, schedule=None, other=None):
+    """other (with a schedule): a second batch of the same size; the two take turns so that every lane's buffers serve both
+    in alternation, and each rank's result gets a fourth entry, the (ids, dists) of `other`."""
     save = A.Save.from_dict(prec, save_arrays)
     td = ThreadDist(world)
     results, errors = [None] * world, []
     yt = torch.from_numpy(np.ascontiguousarray(y)).cuda()
+    yo = torch.from_numpy(np.ascontiguousarray(other)).cuda() if other is not None else None
 
     def work(rank):
         try:
@@ -84,10 +87,20 @@ def _run_sharded(prec, save_arrays, pts, y, world, alias=False, fast=True, pipel
             sq = ShardedQuery(ix, td, exchange="alltoall" if fast else "allgather", lanes=3 if schedule else 2)
             if schedule:     # (lanes in use, two-half issue, CUs kept free of the gathers, launches per gather)
                 sq.configure(*schedule)
-                res = sq.pump([yt] * 5, alias=alias)
-                ids, dd = res[0]
-                for ids1, dd1 in res[1:]:
-                    assert torch.equal(ids, ids1) and torch.equal(dd.view(torch.uint8), dd1.view(torch.uint8))
+                if yo is None:
+                    res = sq.pump([yt] * 5, alias=alias)
+                    ids, dd = res[0]
+                    for ids1, dd1 in res[1:]:
+                        assert torch.equal(ids, ids1) and torch.equal(dd.view(torch.uint8), dd1.view(torch.uint8))
+                else:  # batch i runs on lane i % depth: consecutive batches of one lane differ
+                    turn = [(i // sq.depth + i % sq.depth) % 2 for i in range(6)]
+                    assert all(turn[i] != turn[i + sq.depth] for i in range(6 - sq.depth))
+                    res = sq.pump([(yt, yo)[t] for t in turn], alias=alias)
+                    ids, dd = res[turn.index(0)]
+                    ids_o, dd_o = res[turn.index(1)]
+                    for t, (ids1, dd1) in zip(turn, res):
+                        want_i, want_d = (ids, dd) if t == 0 else (ids_o, dd_o)
+                        assert torch.equal(want_i, ids1) and torch.equal(want_d.view(torch.uint8), dd1.view(torch.uint8))
             elif pipelined:  # two batches in flight on two HIP streams
                 t0, t1 = sq.submit(yt, alias=alias), sq.submit(yt, alias=alias)
                 ids, dd = sq.collect(t0)
@@ -97,6 +110,8 @@ def _run_sharded(prec, save_arrays, pts, y, world, alias=False, fast=True, pipel
                 ids, dd = sq.query(yt, alias=alias)
             torch.cuda.synchronize()
             results[rank] = (ids.cpu().numpy().astype(np.uint64), dd.cpu().numpy(), sq.last_exact)
+            if yo is not None:
+                results[rank] += ((ids_o.cpu().numpy().astype(np.uint64), dd_o.cpu().numpy()),)
             LAST_TIE_QUERIES[rank] = ix.stats()["tie_queries"]  # flagged rows this rank answered without the network
             ix.close()
         except Exception as e:  # noqa: BLE001
@@ -215,6 +230,10 @@ def test_small_shards_with_a_heavy_bucket(prec):
 def test_sharded_precomp_matches_golden(name, world):
     """precomp with its distance passes dealt to the ranks by bucket (power-of-two d) -- or run redundantly where the
     bucket kernel does not apply (d = 80, 100) -- gives the reference's index on every rank, field for field."""
+    sharded_precomp_matches_golden(name, world)
+
+
+def sharded_precomp_matches_golden(name, world):
     from approximatenn_amd.sharded import precomp_sharded
     from tests.util import assert_save_equal
     g = load_golden(name)

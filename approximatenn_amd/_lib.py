@@ -135,6 +135,12 @@ def load(prec="f32"):
     lib.annhip_query_sorted_set.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.annhip_radius_trim.restype = C.c_int
     lib.annhip_radius_trim.argtypes = [sz, sz, sz, vp, vp, vp, vp, vp]
+    lib.annhip_collapse.restype = C.c_int
+    lib.annhip_collapse.argtypes = [sz, sz, sz, sz, C.c_uint32, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.annhip_query_grouped.restype = C.c_long
+    lib.annhip_query_grouped.argtypes = [vp, vp, vp, sz, vp, C.c_int, sz, sz, sz, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+    lib.annhip_index_exact_query_grouped.restype = C.c_int
+    lib.annhip_index_exact_query_grouped.argtypes = [vp, sz, vp, C.c_int, sz, sz, sz, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
     lib.annhip_rerank.restype = C.c_int
     lib.annhip_rerank.argtypes = [sz, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp]
     lib.annhip_index_rerank.restype = C.c_int
@@ -264,6 +270,7 @@ EXPORTED = ["gpu_init", "gpu_cleanup", "register_cleanup", "query_gpu", "precomp
             "annhip_index_sort_tags", "annhip_index_tag_order", "annhip_tag_runs", "annhip_query_sorted",
             "annhip_tag_runs_set", "annhip_query_sorted_set",
             "annhip_rerank", "annhip_index_rerank",
+            "annhip_collapse", "annhip_query_grouped", "annhip_index_exact_query_grouped",
             "annhip_index_append", "annhip_index_reserve_tail", "annhip_index_tail", "annhip_index_copy_rows", "annhip_index_drop_tail",
             "annhip_index_hash_tail", "annhip_index_tail_hashed",
             "annhip_index_fixed", "annhip_index_copy_words",

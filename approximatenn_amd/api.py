@@ -533,6 +533,71 @@ def radius_trim(ids, dists, radius, pad_id):
     return counts
 
 
+def _check_group(what, group, k, per_group):
+    """the arguments every grouped call shares -> (gmask, k, per_group) as ints; ValueError for a bool or non-integer, a
+    group mask that is no non-zero 32-bit word, k < 1 or per_group < 1"""
+    for name, v in (("group", group), ("k", k), ("per_group", per_group)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: %s must be an integer, got %r" % (what, name, v))
+    if not 0 < int(group) <= 0xFFFFFFFF:
+        raise ValueError("%s: group must be a non-zero 32-bit mask, got %r" % (what, group))
+    if int(k) < 1 or int(per_group) < 1:
+        raise ValueError("%s: k and per_group must be at least 1" % what)
+    return int(group), int(k), int(per_group)
+
+
+def collapse(ids, dists, tags, group, k, per_group=1, rows=None, pad_id=None, stream=None):
+    """annhip_collapse: at most per_group entries per group of any list.  ids int64 [Q,L] and dists [Q,L] contiguous device
+    tensors, read in the order given (query(k=), exact_query(k=) and exact_knn give ascending (distance, id), pads last);
+    tags the 32-bit tag words of the rows, a numpy uint32 array or an int32 device tensor; group the mask whose bits of
+    the tag word are the group key -> (ids int64 [Q,k], dists [Q,k], counts int32 [Q], short bool [Q]).  An entry whose
+    id is not in [0, rows) is a pad and skipped (rows=None: len(tags)); a non-pad entry is kept iff fewer than per_group
+    earlier non-pad entries of its row have its key; the first k kept entries are the row, padded with (pad_id, +inf)
+    (pad_id=None: rows); counts = entries kept; short[q] = fewer than k kept although the list held no pad: a longer
+    list might have found more groups.  Distances are copied bit for bit.  Runs on `stream` (the current stream when
+    none is given) and returns at once; the inputs stay as they are (annhip_collapse itself may run in place where
+    k == L).  ValueError for tensors of another kind, a bool or non-integer argument, and where the library refuses (L outside 1..1024, k outside 1..L,
+    per_group < 1, group == 0, rows beyond len(tags) or 32 bits); the outputs are then untouched."""
+    import torch
+    if (not isinstance(ids, torch.Tensor) or not isinstance(dists, torch.Tensor) or not ids.is_cuda or not dists.is_cuda
+            or ids.dtype != torch.int64 or dists.dtype not in (torch.float32, torch.float64) or ids.dim() != 2
+            or ids.shape != dists.shape or not ids.is_contiguous() or not dists.is_contiguous()):
+        raise ValueError("collapse: ids int64 [Q,L] and dists [Q,L] must be contiguous device tensors of one shape")
+    gmask, k, per_group = _check_group("collapse", group, k, per_group)
+    if isinstance(tags, np.ndarray) and tags.ndim != 1 or isinstance(tags, torch.Tensor) and tags.dim() != 1:
+        raise ValueError("collapse: tags must be one-dimensional")
+    tg = _words_dev(tags, len(tags) if hasattr(tags, "__len__") else 0, ids.device, "tags")
+    for name, v in (("rows", rows), ("pad_id", pad_id)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0):
+            raise ValueError("collapse: %s must be a non-negative integer, got %r" % (name, v))
+    rows = tg.shape[0] if rows is None else int(rows)
+    if rows > tg.shape[0]:
+        raise ValueError("collapse: rows = %d exceeds the %d tag words given" % (rows, tg.shape[0]))
+    pad_id = rows if pad_id is None else int(pad_id)
+    Q, L = ids.shape
+    if not 1 <= L <= 1024 or k > L:
+        raise ValueError("collapse: L = %d must be in 1..1024 and k = %d in 1..L" % (L, k))
+    o_ids = torch.empty((Q, k), dtype=torch.int64, device=ids.device)
+    o_dists = torch.empty((Q, k), dtype=dists.dtype, device=ids.device)
+    counts = torch.zeros((Q,), dtype=torch.int32, device=ids.device)
+    short = torch.zeros((Q,), dtype=torch.uint8, device=ids.device)
+    lib = _lib.load("f32" if dists.dtype == torch.float32 else "f64")
+    cur = torch.cuda.current_stream(ids.device)
+    run = stream if stream is not None else cur
+    if run != cur:
+        run.wait_stream(cur)  # the arrays were made on that one
+    hold = torch.empty((1,), dtype=torch.int64, device=ids.device)
+    rc = lib.annhip_collapse(Q, L, k, per_group, gmask, _ptr(tg, hold), rows, pad_id, _ptr(ids, hold), _ptr(dists, hold),
+                             _ptr(o_ids, hold), _ptr(o_dists, hold), counts.data_ptr(), short.data_ptr(), run.cuda_stream)
+    if rc != 0:
+        raise ValueError("annhip_collapse refused L=%d k=%d per_group=%d group=%#x rows=%d" % (L, k, per_group, gmask, rows))
+    if run != cur:  # keep the arrays until the pass has read them
+        for t in (ids, dists, tg, o_ids, o_dists, counts, short, hold):
+            t.record_stream(run)
+        cur.wait_stream(run)  # short.bool() below runs on the current stream
+    return o_ids, o_dists, counts, short.bool()
+
+
 def radius_recall(guess_ids, guess_counts, truth_ids, truth_counts):
     """Recall of a radius query against its ground truth: the mean, over the queries with truth_counts > 0, of
     |guess[q][:guess_counts[q]] ∩ truth[q][:truth_counts[q]]| / truth_counts[q] -> (recall, queries counted); (0.0, 0) where
@@ -1345,6 +1410,91 @@ class Index:
         rad = _radius_dev(radius, Q, y.dtype, y.device)
         pred = _where_dev(where, Q, y.device) if where is not None else None
         return self._exact_call(self._exact_entry(pred, True, True), y, alias, k, rad, pred)
+
+    def _group_args(self, what, y, group, k, per_group, candidates, oversample, where, kmax):
+        """What query_grouped and exact_query_grouped share -> (gmask, k, per_group, K', the three predicate tensors or
+        None); ValueError for a bool or non-integer argument, k or per_group < 1, K' outside k..kmax, a group mask that is
+        no non-zero 32-bit word, a where of wrong shape or dtype and an index without tags."""
+        assert y.is_cuda and y.is_contiguous() and y.dtype == self._torch_ft(self.prec) and y.shape[1] == self.d
+        gmask, k, per_group = _check_group(what, group, self.k if k is None else k, per_group)
+        if candidates is None:
+            if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
+                raise ValueError("%s: oversample must be an integer >= 1, got %r" % (what, oversample))
+            candidates = min(kmax, k * int(oversample))
+        elif isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)):
+            raise ValueError("%s: candidates must be an integer, got %r" % (what, candidates))
+        kc = int(candidates)
+        if not k <= kc <= kmax:
+            raise ValueError("%s: candidates = %d must be in k = %d .. %d" % (what, kc, k, kmax))
+        if not self.has_tags:
+            raise ValueError("%s: the index has no tags (Index.set_tags)" % what)
+        pred = _where_dev(where, y.shape[0], y.device) if where is not None else None
+        if pred is not None and len(pred) == 2:  # the pair is the range whose two bounds are the value
+            pred = (pred[0], pred[1], pred[1])
+        return gmask, k, per_group, kc, pred
+
+    def query_grouped(self, y, group, k=None, per_group=1, candidates=None, oversample=4, where=None, alias=False, ws=None,
+                      stream=None):
+        """annhip_query_grouped: fixed mode's k nearest with at most per_group rows of each group ("the k nearest
+        documents, not the k nearest chunks") -> (ids int64 [Q,k], sq dists [Q,k], counts int32 [Q], short bool [Q]).
+        group: the mask whose bits of the tag word (set_tags, append(tags=)) are the group key.  The row is collapse()
+        of the row of query(k=candidates, where=where): ascending (distance, id), padded with (n_total, +inf);
+        counts = entries that are no pads.  short[q]: fewer than k groups among a full list of candidates -- ask again
+        with more; where short[q] is False the row is exact for the ordering the candidates are a prefix of.  k=None: the
+        index's k; candidates=None: min(max_query_k, k * oversample).  where (pair or triple), alias, ws and stream as in
+        query(k=).  ValueError for a bool or non-integer argument, for k or per_group < 1, candidates outside
+        k..max_query_k, a group that is no non-zero 32-bit mask, an index without tags, and where the library refuses
+        (fixed mode off, a resharded index); nothing is launched then."""
+        import torch
+        gmask, k, per_group, kc, pred = self._group_args("query_grouped", y, group, k, per_group, candidates, oversample, where,
+                                                         self.max_query_k)
+        Q = y.shape[0]
+        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        short = torch.zeros((Q,), dtype=torch.uint8, device=y.device)
+        cur = torch.cuda.current_stream(y.device)
+        if stream is not None and cur != stream:
+            stream.wait_stream(cur)  # the predicate and output arrays were made on that one
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)  # (an empty batch: the library refuses a NULL ids array)
+        rc = self.lib.annhip_query_grouped(self.h, ws, stream.cuda_stream if stream is not None else None, Q, y.data_ptr(),
+                                           int(bool(alias)), kc, k, per_group, gmask,
+                                           *(tuple(t.data_ptr() for t in pred) if pred is not None else (None, None, None)),
+                                           _ptr(ids, hold), dists.data_ptr(), counts.data_ptr(), short.data_ptr())
+        if rc != 0:
+            raise ValueError("annhip_query_grouped refused candidates=%d k=%d per_group=%d (fixed mode off, candidates outside "
+                             "1..%d, or a resharded index)" % (kc, k, per_group, self.max_query_k))
+        if stream is not None:  # keep the arrays until the batch has read them
+            for t in (y, ids, dists, counts, short, hold) + (pred or ()):
+                t.record_stream(stream)
+            if cur != stream:
+                cur.wait_stream(stream)  # short.bool() below runs on the current stream
+        return ids, dists, counts, short.bool()
+
+    def exact_query_grouped(self, y, group, k=None, per_group=1, candidates=None, oversample=4, where=None, alias=False):
+        """annhip_index_exact_query_grouped: the ground truth of query_grouped -- collapse() of the row of
+        exact_query(k=candidates, where=where) on the native rows -> (ids, dists, counts, short) as there.  Where
+        short[q] is False the row is the collapse of ALL valid rows in (distance, id) order.  candidates=None:
+        min(1024, k * oversample).  Synchronous.  ValueError as query_grouped raises it, with 1024 in the place of
+        max_query_k, and where the library refuses (candidates beyond the rows on offer, a resharded index)."""
+        import torch
+        gmask, k, per_group, kc, pred = self._group_args("exact_query_grouped", y, group, k, per_group, candidates, oversample,
+                                                         where, 1024)
+        Q = y.shape[0]
+        ids = torch.empty((Q, k), dtype=torch.int64, device=y.device)
+        dists = torch.empty((Q, k), dtype=y.dtype, device=y.device)
+        counts = torch.zeros((Q,), dtype=torch.int32, device=y.device)
+        short = torch.zeros((Q,), dtype=torch.uint8, device=y.device)
+        torch.cuda.current_stream(y.device).synchronize()  # the scan runs on the null stream
+        hold = torch.empty((1,), dtype=torch.int64, device=y.device)
+        rc = self.lib.annhip_index_exact_query_grouped(
+            self.h, Q, y.data_ptr(), int(bool(alias)), kc, k, per_group, gmask,
+            *(tuple(t.data_ptr() for t in pred) if pred is not None else (None, None, None)),
+            _ptr(ids, hold), _ptr(dists, hold), counts.data_ptr(), short.data_ptr())
+        if rc != 0:
+            raise ValueError("annhip_index_exact_query_grouped refused candidates=%d k=%d per_group=%d (candidates beyond the "
+                             "rows on offer, or a resharded index)" % (kc, k, per_group))
+        return ids, dists, counts, short.bool()
 
     def host_stream(self, max_ycnt, lanes=3):
         """annhip_stream_open: pipeline for host-resident (numpy) batches; see HostStream."""

@@ -35,6 +35,7 @@
 #include "ann_rerank_kernels.h"
 #include "ann_prune_kernels.h"
 #include "ann_sorted_kernels.h"
+#include "ann_group_kernels.h"
 
 static_assert(sizeof(ftype) == sizeof(FT), "ftype.h and ann_device.h disagree on the precision");
 
@@ -274,6 +275,7 @@ struct annhip_workspace {
   DevBuf pbits;  // fixed mode with pair bits: u8[Q][T][b] ranked projection indices of this batch (annhip_index_set_probe)
   DevBuf sorted;  // annhip_query_sorted: u32 start[Q], len[Q], list[Q][3], qmask[Q]
   DevBuf tie_d, tie_i;  // pruned stage 1: [Q][k+1] exact candidate lists of the flagged queries (PruneArgs::tie_d / tie_i)
+  DevBuf grp_i, grp_d;  // annhip_query_grouped: the [Q][list] result that the collapse reads (size_t ids, FT dists)
   // annhip_query_sorted_set: the staging that the interval count sizes, the arrays that the entry count sizes, and the
   // pinned copy of the call's offsets with the event that says the previous call's upload has read it
   DevBuf sset, spart;
@@ -284,7 +286,7 @@ struct annhip_workspace {
     sset.release(), spart.release(), spin.release();
     if (sset_ev) HIPCHECK(hipEventDestroy(sset_ev));
     sset_ev = NULL;
-    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted, &tie_d, &tie_i};
+    DevBuf *bufs[] = {&codes, &cand_d, &cand_i, &nvt, &nvo, &top_i, &top_d, &flist, &xids, &xd, &r2i, &r2d, &out_i, &out_d, &pbits, &sorted, &tie_d, &tie_i, &grp_i, &grp_d};
     for (DevBuf *b : bufs) b->release();
     if (d_fcount) HIPCHECK(hipFree(d_fcount));
     d_fcount = NULL;
@@ -1738,6 +1740,15 @@ static void launch_tail_hash_merge(annhip_index *ix, size_t Q, const FT *y, size
                                    hipStream_t s);
 static void launch_radius_trim(size_t Q, size_t kcap, size_t pad_id, const FT *radius, size_t *ids, FT *dists, u32 *counts,
                                hipStream_t s);
+// What a grouped call adds to its list of kq = L entries: the collapse (ann_group_kernels.h) into the caller's [Q][k].
+struct GroupCall {
+  size_t k, per_group;
+  u32 gmask;
+  u32 *counts;           // may be NULL
+  unsigned char *shrt;   // may be NULL
+};
+static void launch_collapse(size_t Q, size_t L, const GroupCall &g, const u32 *tags, size_t rows, size_t pad_id, const size_t *ids_in,
+                            const FT *dists_in, size_t *ids_out, FT *dists_out, hipStream_t s);
 
 // How a call of the query path ends: the marks padded to the seven that annhip_stats reads (a path with fewer stages
 // leaves its last segments at zero) and handed over, and the index's counter.
@@ -1754,6 +1765,7 @@ struct FixedCall {
   const TagQuery *tq;  // the tag family of stage 1 and stage 2, or NULL
   const FT *radius;    // annhip_query_radius / _between: stage1_radius_kernel and the trim with counts; stage2_kq only
   u32 *counts;
+  const GroupCall *group;  // annhip_query_grouped: the [Q][kq] result goes to the workspace, its collapse to the caller; or NULL
 };
 static long fixed_query(annhip_index *ix, annhip_workspace &ws, hipStream_t s, size_t Q, const ftype *y_dev, int alias,
                         const FixedCall &c, size_t *ids_dev, ftype *dists_dev, int codes_ready = 0);
@@ -2090,7 +2102,14 @@ static long fixed_query(annhip_index *ix, annhip_workspace &ws, hipStream_t s, s
                      cand_i, nvt, top_i, top_d, (int)kq, 0, (u32 *)NULL, (u32 *)NULL, (unsigned long long *)NULL, P.n);
   HIPCHECK(hipGetLastError());
   seg_mark(ix, marks, s);
-  FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * kq);
+  // (what the caller's rows hold: kq entries, or the k of a grouped call)
+  FT *out_d = dists_dev ? reinterpret_cast<FT *>(dists_dev) : (FT *)ws.out_d.need(sizeof(FT) * Q * (c.group ? c.group->k : kq));
+  size_t *const caller_ids = ids_dev;
+  FT *const caller_d = out_d;
+  if (c.group) {  // the list of kq entries stays in the workspace
+    ids_dev = (size_t *)ws.grp_i.need(sizeof(size_t) * Q * kq);
+    out_d = (FT *)ws.grp_d.need(sizeof(FT) * Q * kq);
+  }
   unsigned long long *scored = ix->profile == 1 ? ix->d_rows + 8 : NULL;
   // two stage 2s, different kernels: a call with the index's own k keeps its selection path, annhip_query_k and the
   // radius calls keep stage2_kq_kernel even where kq == ix->k
@@ -2107,6 +2126,8 @@ static long fixed_query(annhip_index *ix, annhip_workspace &ws, hipStream_t s, s
   // (in profile mode the trim's time falls into the segment of the tail merges: annhip_stage_ms reports no tail segment,
   // so the trim is in neither the stage-1 nor the stage-2 figure)
   if (c.radius) launch_radius_trim(Q, kq, n_total(ix), c.radius, ids_dev, out_d, c.counts, s);
+  // (likewise the collapse of a grouped call)
+  if (c.group) launch_collapse(Q, kq, *c.group, ix->tags, n_total(ix), n_total(ix), ids_dev, out_d, caller_ids, caller_d, s);
   finish_call(ix, marks, s, Q);
   return 0;
 }
@@ -2177,6 +2198,62 @@ extern "C" int annhip_radius_trim(size_t ycnt, size_t kcap, size_t pad_id, const
   launch_radius_trim(ycnt, kcap, pad_id, reinterpret_cast<const FT *>(radius_dev), ids_dev, reinterpret_cast<FT *>(dists_dev),
                      counts_dev, (hipStream_t)hip_stream);
   return 0;
+}
+
+// ----------------------------------------------------------------------------- grouped queries (annhip_query_grouped)
+// Contract: include/ann_hip.h.  Kernel: ann_group_kernels.h.
+static void launch_collapse(size_t Q, size_t L, const GroupCall &g, const u32 *tags, size_t rows, size_t pad_id, const size_t *ids_in,
+                            const FT *dists_in, size_t *ids_out, FT *dists_out, hipStream_t s) {
+  if (!Q) return;
+  const size_t blocks = (Q + ANN_GROUP_WAVES - 1) / ANN_GROUP_WAVES;  // one wave per row
+  if (blocks > 0x7FFFFFFFull) die("collapse: batch too large");
+  const size_t smem = group_lds_bytes(L);
+  allow_lds(group_collapse_kernel, smem);
+  hipLaunchKernelGGL(group_collapse_kernel, dim3((unsigned)blocks), dim3(64 * ANN_GROUP_WAVES), smem, s, Q, (int)L, (int)g.k,
+                     (u32)std::min<size_t>(g.per_group, 0xFFFFFFFFull), g.gmask, tags, (u64)rows, pad_id, ids_in, dists_in, ids_out,
+                     dists_out, g.counts, g.shrt);
+  HIPCHECK(hipGetLastError());
+}
+
+extern "C" int annhip_collapse(size_t ycnt, size_t L, size_t k, size_t per_group, uint32_t gmask, const uint32_t *tags_dev, size_t rows,
+                               size_t pad_id, const size_t *ids_in, const ftype *dists_in, size_t *ids_out, ftype *dists_out,
+                               uint32_t *counts_dev, uint8_t *short_dev, void *hip_stream) {
+  if (L < 1 || L > 1024 || k < 1 || k > L || !per_group || !gmask || !tags_dev || !ids_in || !dists_in || !ids_out || !dists_out ||
+      rows >= 0xFFFFFFF0ull)
+    return -1;
+  if (!ycnt) return 0;
+  gpu_init();
+  launch_collapse(ycnt, L, GroupCall{k, per_group, gmask, counts_dev, short_dev}, tags_dev, rows, pad_id, ids_in,
+                  reinterpret_cast<const FT *>(dists_in), ids_out, reinterpret_cast<FT *>(dists_out), (hipStream_t)hip_stream);
+  return 0;
+}
+
+// what both grouped entries refuse of the grouping itself: its text or NULL
+static const char *group_refusal(size_t list, size_t k, size_t per_group, uint32_t gmask) {
+  return !gmask       ? "gmask must not be 0"
+         : !per_group ? "per_group must be at least 1"
+         : !k || k > list ? "k outside 1..list"
+                          : NULL;
+}
+static const char *all_or_none(const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev) {
+  const int given = (qmask_dev != NULL) + (qlo_dev != NULL) + (qhi_dev != NULL);
+  return given != 0 && given != 3 ? "qmask_dev, qlo_dev and qhi_dev must all be given, or none" : NULL;
+}
+
+// A refusal launches nothing and leaves the outputs untouched; this entry never aborts on what it can refuse.
+extern "C" long annhip_query_grouped(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, const ftype *y_dev,
+                                     int alias, size_t list, size_t k, size_t per_group, uint32_t gmask, const uint32_t *qmask_dev,
+                                     const uint32_t *qlo_dev, const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev,
+                                     uint32_t *counts_dev, uint8_t *short_dev) {
+  if (fixed_refusal(ix, "annhip_query_grouped", true,
+                    {!ix->tags ? NO_TAGS : NULL, group_refusal(list, k, per_group, gmask),
+                     !query_k_fits(make_params(ix), list) ? "list outside 1..annhip_index_max_query_k" : NULL,
+                     all_or_none(qmask_dev, qlo_dev, qhi_dev), !ids_dev ? "ids_dev must be given" : NULL}))
+    return -2;
+  const TagQuery tq{ix->tags, qmask_dev, qlo_dev, qhi_dev};
+  const GroupCall g{k, per_group, gmask, counts_dev, short_dev};
+  return fixed_query(ix, ws ? *ws : ix->ws, (hipStream_t)hip_stream, ycnt, y_dev, alias,
+                     FixedCall{list, true, qmask_dev ? &tq : NULL, NULL, NULL, &g}, ids_dev, dists_dev);
 }
 
 extern "C" long annhip_query_slice(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt, size_t q_lo, size_t nq,
@@ -3096,6 +3173,30 @@ extern "C" int annhip_index_exact_query_between(annhip_index *ix, size_t ycnt, c
   if (const int rc = index_exact_refusal(ix, args, true)) return rc;
   if (const int rc = index_exact(ix, ycnt, y_dev, alias, kq, qmask_dev, qlo_dev, qhi_dev, ids_dev, dists_dev)) return rc;
   return radius_dev ? exact_trim(ix, ycnt, kq, radius_dev, ids_dev, dists_dev, counts_dev) : 0;
+}
+
+// Contract: include/ann_hip.h.  annhip_index_exact_query_k / _between with kq = list into a buffer of the call's own, then
+// the collapse into the caller's arrays: the ground truth of annhip_query_grouped.  Synchronous, on the null stream.
+extern "C" int annhip_index_exact_query_grouped(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias, size_t list, size_t k,
+                                                size_t per_group, uint32_t gmask, const uint32_t *qmask_dev, const uint32_t *qlo_dev,
+                                                const uint32_t *qhi_dev, size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev,
+                                                uint8_t *short_dev) {
+  const char *args = all_or_none(qmask_dev, qlo_dev, qhi_dev);
+  if (!args) args = group_refusal(list, k, per_group, gmask);
+  if (!args && (!ids_dev || !dists_dev)) args = "ids_dev and dists_dev must both be given";
+  if (const int rc = index_exact_refusal(ix, args, true)) return rc;  // (tagged: the group key needs the tags)
+  if (const int rc = exact_check(n_total(ix), ix->d, list, alias)) return rc;
+  if (!ycnt) return 0;
+  size_t *li = dev_alloc<size_t>(ycnt * list);
+  FT *ld = dev_alloc<FT>(ycnt * list);
+  const int rc = index_exact(ix, ycnt, y_dev, alias, list, qmask_dev, qlo_dev, qhi_dev, li, reinterpret_cast<ftype *>(ld));
+  if (!rc)
+    launch_collapse(ycnt, list, GroupCall{k, per_group, gmask, counts_dev, short_dev}, ix->tags, n_total(ix), n_total(ix), li, ld,
+                    ids_dev, reinterpret_cast<FT *>(dists_dev), 0);
+  HIPCHECK(hipStreamSynchronize(0));
+  HIPCHECK(hipFree(li));
+  HIPCHECK(hipFree(ld));
+  return rc;
 }
 
 // ----------------------------------------------------------------------------- the sorted scan (annhip_query_sorted)

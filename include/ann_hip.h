@@ -684,6 +684,66 @@ int annhip_exact_knn_between(size_t n, size_t d, size_t k, const ftype *points_d
                              const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
                              size_t *ids_dev, ftype *dists_dev);
 
+/* ---- grouped queries: at most per_group results per tag group, by collapse ----------------------------- */
+/* "The k nearest documents, not the k nearest chunks": rows that share a document, product or author carry the same value
+ * in a bit field of their tag word, and a grouped call returns at most per_group rows of each value.
+ * Group key: the key of row i for a call is tags[i] & gmask; gmask is one u32 per call, not per query.  tags is the index's
+ * tag array (annhip_index_set_tags, annhip_index_append): one array over the built rows and then the tail rows, tail row j
+ * has id n + j.
+ * Collapse takes a list of L entries (id, dist) per query in the order given -- for the query calls ascending
+ * (distance, id), pads last -- and works as follows with per_group = g:
+ *   - an entry with id >= rows is a pad: it is skipped and never dereferenced.  The test is made on all 64 bits before
+ *     anything is narrowed, as annhip_rerank does: an int64 -1 and 2^32 + 5 are pads;
+ *   - a non-pad entry j is KEPT iff fewer than g earlier non-pad entries i < j have the same key;
+ *   - the output row is the first k kept entries in list order, padded with (pad_id, +inf);
+ *   - counts[q] = the number of kept entries written, at most k;
+ *   - short[q] = 1 iff counts[q] < k and the input list was full, i.e. none of its L entries was a pad: a longer list might
+ *     have found more groups, ask again with more candidates.  Otherwise 0;
+ *   - distances are never compared or recomputed: they are copied bit for bit, NaN and +inf are ordinary values;
+ *   - a repeated id is an ordinary second entry (query results have none).
+ * Prefix stability: whether an entry is kept depends on the entries in front of it only.  Hence
+ *   collapse(first L entries of an ordering)[:k] == collapse(the whole ordering)[:k]
+ * whenever the left side has k entries or the prefix was not full -- with short[q] == 0 the row of a grouped query is
+ * EXACTLY the collapse of the whole ordering its list is a prefix of, not a heuristic cut of it.
+ * annhip_collapse: the stand-alone pass for any [ycnt][L] list: ids_in size_t[ycnt][L], dists_in ftype[ycnt][L] ->
+ * ids_out size_t[ycnt][k], dists_out ftype[ycnt][k], counts_dev u32[ycnt] (may be NULL), short_dev u8[ycnt] (may be NULL).
+ * Input stride L, output stride k; the outputs may be the inputs themselves only where k == L (a row is read whole before
+ * any of it is written).  Runs on hip_stream (NULL: the null stream), needs no workspace and synchronises nothing; 0 = the
+ * launch is queued.  Returns -1 with nothing launched and the outputs untouched: L outside 1..1024; k outside 1..L;
+ * per_group == 0; gmask == 0; a NULL tags_dev, ids_in, dists_in, ids_out or dists_out; rows >= 0xFFFFFFF0.  ycnt == 0 (with
+ * arguments that pass these tests) returns 0 and launches nothing.
+ * annhip_query_grouped: a fixed-mode call.  Its row is, bit for bit, annhip_collapse applied to the row of
+ * annhip_query_between(kq = list) -- with the three predicate arrays NULL, of annhip_query_k(kq = list) -- with the index's
+ * tags and rows = pad_id = n_total.  The list of `list` entries stays in the workspace; ids_dev size_t[ycnt][k], dists_dev
+ * ftype[ycnt][k] (may be NULL), counts_dev, short_dev (each may be NULL) are all the call writes.  Stage 2 is that of
+ * annhip_query_k whatever list is, and the tail merges run before the collapse: appended rows are grouped too, hashed or
+ * fresh.  ws and hip_stream as in annhip_query_k.  Asynchronous; returns 0.  Returns -2, with one line on stderr, nothing
+ * launched and the outputs untouched: while fixed mode is off; on a resharded index; on an index without tags; for
+ * gmask == 0; per_group == 0; k == 0 or k > list; list outside 1..annhip_index_max_query_k(ix); when some but not all of
+ * qmask_dev, qlo_dev, qhi_dev are given; for ids_dev == NULL.  ycnt == 0 (with arguments that pass these tests) returns 0.
+ * Composes with annhip_index_set_probe, annhip_index_set_filter, annhip_index_set_rows, alias, and several workspaces on
+ * several streams.  NOT covered: a radius, parity mode, annhip_stream_*, annhip_sh_*, query_gpu, the sorted scans
+ * (annhip_query_sorted / _sorted_set: collapse their result with annhip_collapse).  Every existing entry point launches
+ * exactly what it launched before.
+ * annhip_index_exact_query_grouped: the ground truth -- the same collapse over the row of
+ * annhip_index_exact_query_between / _k with kq = list: native rows, the allow list honoured, all n_total rows.
+ * Synchronous.  Non-zero with the outputs untouched: that call's refusals (a resharded index, list outside 1..1024 or
+ * beyond the rows a query can be given, a row too long for the LDS of one CU) and the grouped ones above (no tags, gmask,
+ * per_group, k, some but not all predicate arrays, a NULL ids_dev) and a NULL dists_dev.
+ * What the collapse costs beside the step that feeds it is measured, not promised: DESIGN.md §6, tools/group_bench.py. */
+int annhip_collapse(size_t ycnt, size_t L, size_t k, size_t per_group, uint32_t gmask,
+                    const uint32_t *tags_dev, size_t rows, size_t pad_id,
+                    const size_t *ids_in, const ftype *dists_in, size_t *ids_out, ftype *dists_out,
+                    uint32_t *counts_dev /* may be NULL */, uint8_t *short_dev /* may be NULL */, void *hip_stream);
+long annhip_query_grouped(annhip_index *ix, annhip_workspace *ws, void *hip_stream, size_t ycnt,
+                          const ftype *y_dev, int alias, size_t list /* K' */, size_t k, size_t per_group, uint32_t gmask,
+                          const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                          size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev, uint8_t *short_dev);
+int annhip_index_exact_query_grouped(annhip_index *ix, size_t ycnt, const ftype *y_dev, int alias,
+                                     size_t list, size_t k, size_t per_group, uint32_t gmask,
+                                     const uint32_t *qmask_dev, const uint32_t *qlo_dev, const uint32_t *qhi_dev,
+                                     size_t *ids_dev, ftype *dists_dev, uint32_t *counts_dev, uint8_t *short_dev);
+
 /* ---- the tag order: exact answers for selective predicates by sorted scan ----------------------------- */
 /* Where a predicate is selective, do not search the ANN structure: scan exactly the rows that match.  If the row ids are
  * sorted by tags & field_mask, every pair or range predicate on that mask matches a contiguous run of the sorted order.
